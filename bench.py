@@ -22,6 +22,16 @@ the owners' order-independent output digests combine into the whole job's parity
 Extra JSON keys: roofline (the counting pass vs 8 TB/s HBM; traffic from the committed
 PMC summary profiles/pmc_traffic.json when it matches the workload), cpu_baseline (the
 reference CLI oracle/_ref/kaarme on a bounded sample of the same workload, rank 0, N=1).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets the job up, warms up, times the N
+steps and prints the line: its headline figures and what the timed steps' own events give
+(roofline, kernel_ms).  --full adds every other record, each a run of its own: the C3 / C4 / C5
+workloads beside C2 (N > 1: C2 beside C4), the CPU baseline, the parity digests against the
+reference, the writer, the compact representation, the drop-in CLI at full size and the C-ABI
+host-chunk path (each still has its own --no-... switch under --full).
+
+--dump-outputs DIR writes what the last timed step left in the table, as a caller of
+kc_dump / kc_output_digest receives it, to DIR/<name>.npy (float64; see dump_outputs).
 """
 import argparse
 import ctypes
@@ -659,6 +669,86 @@ def writer_record(job, verify):
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files of one run together
+DUMP_HOST_BYTES = 8 << 30  # the largest kc_dump record array a dump copies to the host
+
+
+def _mix64(x):
+    """splitmix64's finaliser on a uint64 array (wrapping arithmetic)."""
+    import numpy as np
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _halves(a):
+    """uint64 array (..., n) -> float64 (..., 2n): the high and low 32 bits of every word, both
+    exact in float64."""
+    import numpy as np
+    a = np.asarray(a, dtype=np.uint64)
+    out = np.empty(a.shape[:-1] + (2 * a.shape[-1],), dtype=np.float64)
+    out[..., 0::2] = (a >> np.uint64(32)).astype(np.float64)
+    out[..., 1::2] = (a & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    return out
+
+
+def sample_records(recs, seed, max_records):
+    """A fixed sample of kc_dump records (n, W + 1), in an order of its own: the records whose
+    seeded key hash has its low s bits clear, s the smallest for which the expected sample stays
+    within 0.8 x max_records, sorted by key.  It depends on the keys alone, not on where the
+    table holds them or in which order the dump kernel emitted them.  Returns (records, s)."""
+    import numpy as np
+    n, W = recs.shape[0], recs.shape[1] - 1
+    s = 0
+    while (n >> s) > 0.8 * max_records:
+        s += 1
+    if s:
+        h = np.full(n, (seed * 0x9E3779B97F4A7C15 + 1) & (2**64 - 1), dtype=np.uint64)
+        for w in range(W):
+            h = _mix64(h ^ recs[:, w])
+        recs = recs[(h & np.uint64((1 << s) - 1)) == 0]
+    order = np.lexsort([recs[:, w] for w in range(W - 1, -1, -1)])
+    return recs[order][:max_records], s
+
+
+def dump_outputs(job, st, args, prefix=""):
+    """--dump-outputs: what the last timed step computed, as float64 .npy files in args.dump_outputs
+    (at most DUMP_MAX_BYTES together), comparable file for file between two builds:
+      stats.npy   [windows, inserted, distinct] of the job (kc_finish)
+      digest.npy  kc_output_digest of the whole output: [lines, count_sum, hash_sum hi32, lo32,
+                  hash_xor hi32, lo32]
+      keys.npy    (n, 2 W): a seeded sample (sample_records) of the kc_dump records, sorted by key;
+                  every 64-bit key word as its high and low 32 bits
+      counts.npy  (n,): T(c) of the same records
+      sample.npy  [records dumped, log2 of the sampling stride, records kept]
+    keys / counts / sample are left out when the record array is beyond DUMP_HOST_BYTES on the
+    host (the whole C4 / C5 jobs): the digest still covers every output line."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+
+    def save(name, arr):
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        np.save(os.path.join(args.dump_outputs, prefix + name + ".npy"), arr)
+        return arr.nbytes + 128
+
+    d = job.counter.output_digest()
+    hs, hx = int(d["hash_sum"], 16), int(d["hash_xor"], 16)
+    used = save("stats", [st["windows"], st["inserted"], st["distinct"]])
+    used += save("digest", [d["lines"], d["count_sum"], hs >> 32, hs & 0xFFFFFFFF, hx >> 32, hx & 0xFFFFFFFF])
+    import kaarme_amd as ka
+    W = ka.words_for_k(args.k)
+    if st["distinct"] * (W + 1) * 8 > DUMP_HOST_BYTES:
+        log(f"--dump-outputs: {st['distinct']} records stay on the device (stats and digest only)")
+        return
+    recs = job.counter.dump()
+    per_record = (2 * W + 1) * 8
+    kept, s = sample_records(recs, args.seed, (DUMP_MAX_BYTES - used - 1024) // per_record)
+    used += save("keys", _halves(kept[:, :W]))
+    used += save("counts", kept[:, W].astype(np.float64))
+    used += save("sample", [recs.shape[0], s, kept.shape[0]])
+    assert used <= DUMP_MAX_BYTES, used
+
+
 def run_workload(args, env, image=None):
     """Times one workload (warmup + steps of a full counting job) and returns its JSON record
     plus the device image (reusable by a workload with the same generator parameters)."""
@@ -729,8 +819,11 @@ def run_workload(args, env, image=None):
                             "for); model = the job's windows / G x the bytes per window at G (superkmer_windows_per_run, runs of one owner "
                             "merging G / (G - 1) super-k-mers) x (G - 1) / G")
     st = counter.finish()  # raises on table overflow
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(job, st, args, f"rank{rank}_" if world > 1 else "")
     if rank == 0:
-        log(f"{args.config}: {args.steps} steps in {elapsed:.3f} s; parity / writer records")
+        log(f"{args.config}: {args.steps} steps in {elapsed:.3f} s"
+            + ("; parity / writer records" if args.verify or args.writer else ""))
     parity = parity_record(job, k, dist) if args.verify else None
     # (the text writer and its sorted-file digest for outputs up to ~8 GB: C2 / C3; a strong
     # share's 30 GB of text would take minutes to sort)
@@ -1036,7 +1129,21 @@ def main():
     ap.add_argument("--launch-only", action="store_true",
                     help="start the ranks, join the process group and print the line without any GPU work "
                          "(tests the N-rank launch on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="every record beside the headline line: the other workloads (c3 / c4 / c5; N > 1: c2), the "
+                         "CPU baseline, parity digests, writer, compact, cli_fullsize and c_abi_host_chunks records "
+                         "(each with its own --no-... switch); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (stats, output digest, a seeded "
+                         "sample of the {key, count} records) as float64 DIR/<name>.npy, 64 MB at most")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run times the headline workload and nothing else
+        args.no_cpu_baseline = True
+        args.compact = args.verify = args.cli_fullsize = args.host_chunks = args.writer = False
+        args.secondary = args.tertiary = args.quaternary = args.multi_secondary = "none"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `bench.py --gpus N` without a launcher starts its own N rank processes
         # (before anything here touches the GPU) instead of timing one GPU
@@ -1098,6 +1205,7 @@ def main():
         extra.append((args.multi_secondary, {}))
     for name, over in extra:
         sec = resolve(args, name)
+        sec.dump_outputs = None  # (the headline workload's outputs only)
         for key, val in over.items():
             setattr(sec, key, val)
         if not same_image(primary, sec):

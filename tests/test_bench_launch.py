@@ -81,7 +81,7 @@ def test_two_rank_line_rehearsed_on_one_gpu_matches_one_gpu():
     """The N > 1 line's code path end to end (--rehearse-one-gpu: two ranks on cuda:0 over gloo):
     the default strong C4 line at a small read count with its c2 record and xgmi record, whose
     combined owner digest equals the same job's on one GPU."""
-    common = ["--reads", "200000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-compact",
+    common = ["--full", "--reads", "200000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-compact",
               "--no-writer", "--no-cli-fullsize"]
     p2 = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--rehearse-one-gpu"] + common, capture_output=True,
                         text=True, timeout=500, env=_env())
