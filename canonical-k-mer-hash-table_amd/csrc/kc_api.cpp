@@ -2535,6 +2535,80 @@ int kc_compact_lookup(kc_ctx* c, const uint64_t* keys, uint64_t n, uint32_t* cou
     return KC_OK;
 }
 
+// ------------------------------------------------------------------------------
+// Queries of the counted full-key table: kc_query_impl.h (the reference has none: its table
+// is only walked by the writers, kmer_hash_table.cpp:4318-4524)
+// ------------------------------------------------------------------------------
+int kc_lookup_device(kc_ctx* c, const uint64_t* keys, uint64_t n, int layout, uint32_t* counts, void* sp) {
+    if (!c) return KC_ERR_ARG;
+    if (layout != KC_KEYS_DUMP && layout != KC_KEYS_TABLE) return c->fail(KC_ERR_ARG, "unknown key layout");
+    if (n && (!keys || !counts)) return c->fail(KC_ERR_ARG, "null key or count array");
+    JOB_OK(c);
+    if (!c->nbuckets) return c->fail(KC_ERR_STATE, "no table (kc_bloom_finalize must precede a lookup)");
+    if (n == 0) return KC_OK;
+    hipStream_t s = pick_stream(c, sp);
+    int rc = flush_host(c);
+    if (rc) return rc;
+    if (s != c->stream) {
+        HIPCHK(c, hipEventRecord(c->xev, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(s, c->xev, 0));
+    }
+    rc = materialize_zero(c, s);  // an emptied table answers 0
+    if (rc) return rc;
+    HIPCHK(c, launch_lookup(table_view(c), c->cfg.k, c->cfg.mode == 0 ? 0 : 1, layout, keys, n, counts, s));
+    if (s != c->stream) {  // the context's later work (counting into the table) follows the lookup
+        HIPCHK(c, hipEventRecord(c->xev, s));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->xev, 0));
+    }
+    return KC_OK;
+}
+
+int kc_lookup(kc_ctx* c, const uint64_t* keys, uint64_t n, int layout, uint32_t* counts) {
+    if (!c) return KC_ERR_ARG;
+    if (layout != KC_KEYS_DUMP && layout != KC_KEYS_TABLE) return c->fail(KC_ERR_ARG, "unknown key layout");
+    if (n && (!keys || !counts)) return c->fail(KC_ERR_ARG, "null key or count array");
+    JOB_OK(c);
+    if (!c->nbuckets) return c->fail(KC_ERR_STATE, "no table (kc_bloom_finalize must precede a lookup)");
+    if (n == 0) return KC_OK;
+    uint64_t* dk = nullptr;
+    uint32_t* dc = nullptr;
+    make_room(c, n * (c->W * 8 + 4));
+    if (hipMalloc(&dk, n * c->W * 8) != hipSuccess || hipMalloc(&dc, n * 4) != hipSuccess) {
+        hipFree(dk);
+        return c->fail(KC_ERR_NOMEM, "lookup buffers");
+    }
+    hipError_t e = hipMemcpyAsync(dk, keys, n * c->W * 8, hipMemcpyHostToDevice, c->stream);
+    int rc = e == hipSuccess ? kc_lookup_device(c, dk, n, layout, dc, c->stream) : c->hipfail(e, "lookup: key copy");
+    if (rc == KC_OK) {
+        e = hipMemcpyAsync(counts, dc, n * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = c->hipfail(e, "lookup: count copy");
+    } else {
+        (void)hipStreamSynchronize(c->stream);  // (the key copy reads dk)
+    }
+    hipFree(dk);
+    hipFree(dc);
+    return rc;
+}
+
+int kc_histogram(kc_ctx* c, uint64_t* hist, uint32_t n_bins) {
+    if (!c) return KC_ERR_ARG;
+    if (!hist || n_bins < 2 || n_bins > 65537) return c->fail(KC_ERR_ARG, "kc_histogram: 2 <= n_bins <= 65537");
+    int rc = sync_for_read(c);
+    if (rc) return rc;
+    if (!c->nbuckets) return c->fail(KC_ERR_STATE, "no table");
+    unsigned long long* d = nullptr;
+    const size_t bytes = (size_t)n_bins * sizeof(unsigned long long);
+    if (hipMalloc(&d, bytes) != hipSuccess) return c->fail(KC_ERR_NOMEM, "histogram buffer allocation failed");
+    hipError_t e = hipMemsetAsync(d, 0, bytes, c->stream);
+    if (e == hipSuccess) e = launch_histo(table_view(c), c->cfg.mode == 0 ? 0 : 1, n_bins, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, d, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(d);
+    if (e != hipSuccess) return c->fail(KC_ERR_HIP, std::string("histogram: ") + hipGetErrorString(e));
+    return KC_OK;
+}
+
 int kc_compact_read(kc_ctx* c, uint64_t* words, uint64_t n_words, uint64_t* second, uint64_t n_second_words) {
     if (!c) return KC_ERR_ARG;
     if (!c->d_cwords) return c->fail(KC_ERR_STATE, "no compact representation (kc_compact)");

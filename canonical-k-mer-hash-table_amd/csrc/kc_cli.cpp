@@ -58,6 +58,9 @@ struct Args {
     bool host_chunks = false, no_warmup = false, phases = false, digest_only = false;
     int table_sizing = 0;  // --table-sizing auto (0) | s (1) | estimate (2)
     unsigned readers = 1;
+    // extensions that query the counted table (kc_histogram / kc_lookup): --histo FILE writes the
+    // abundance spectrum, --query FILE --query-out FILE answers one k-mer per line
+    std::string histo, query, query_out;
 };
 
 void usage(const char* prog) {
@@ -76,7 +79,10 @@ void usage(const char* prog) {
                  "  -f,--bfilter-fpr FLOAT      Bloom filter false positive rate (def. 0.01)\n"
                  "  --device INT                HIP device ordinal (def. 0)\n"
                  "  --strict-capacity           fail like the reference once the distinct k-mers pass its table\n"
-                 "                              size next_prime3mod4(-s) (the device table keeps 25 % headroom)\n\n"
+                 "                              size next_prime3mod4(-s) (the device table keeps 25 % headroom)\n"
+                 "  --histo FILE                write the abundance spectrum \"<count> <k-mers>\" (not filtered by -a)\n"
+                 "  --query FILE                k-mers to look up, one per line (either strand, any case)\n"
+                 "  --query-out FILE            their counts \"<k-mer> <count>\" (0 = absent); needed with --query\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -245,6 +251,12 @@ int parse(int argc, char** argv, Args* a) {
                 else if (v == "s") a->table_sizing = 1;
                 else if (v == "estimate") a->table_sizing = 2;
                 else return cli_error(kValidation, o + ": Value " + v + " not in {auto, s, estimate}");
+            } else if (o == "--histo") {
+                a->histo = v;
+            } else if (o == "--query") {
+                a->query = v;
+            } else if (o == "--query-out") {
+                a->query_out = v;
             } else if (o == "--readers") {
                 if (!parse_int(v, &si) || si < 1 || si > 16) return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 a->readers = (unsigned)si;
@@ -269,6 +281,8 @@ int parse(int argc, char** argv, Args* a) {
     if (a->use_bf && !a->have_u) return cli_error(kRequires, "--use-bfilter requires --unq-kmers");
     if (a->have_u && !a->use_bf) return cli_error(kRequires, "--unq-kmers requires --use-bfilter");
     if (a->fpr_set && !a->use_bf) return cli_error(kRequires, "--bfilter-fpr requires --use-bfilter");
+    if (!a->query.empty() && a->query_out.empty()) return cli_error(kRequires, "--query requires --query-out");
+    if (a->query.empty() && !a->query_out.empty()) return cli_error(kRequires, "--query-out requires --query");
     return -1;
 }
 
@@ -430,12 +444,66 @@ struct Upload {
     }
 };
 
+// --query FILE: one k-mer per line (A/C/G/T in any case, either strand; CRLF tolerated, empty
+// lines skipped) -> the lines as given and their keys in the kc_dump layout, W words each.  A line
+// of length k with another character gets a key that is no k-mer (bit 63 of word 0), which
+// kc_lookup answers with 0.  Returns -1 on success, else the exit code (a line of another
+// length is a usage error).
+int read_queries(const std::string& path, int k, std::vector<std::string>* lines, std::vector<uint64_t>* keys) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return cli_error(kValidation, "--query: File does not exist: " + path);
+    const int W = k / 32 + 1;
+    std::string line;
+    unsigned long long lineno = 0;
+    bool eof = false;
+    while (!eof) {
+        line.clear();
+        int ch;
+        while ((ch = std::fgetc(f)) != EOF && ch != '\n') line.push_back((char)ch);
+        eof = ch == EOF;
+        if (eof && line.empty()) break;
+        lineno++;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        if (line.size() != (size_t)k) {
+            std::fclose(f);
+            return cli_error(kValidation, "--query: line " + std::to_string(lineno) + " of " + path + " has " +
+                                              std::to_string(line.size()) + " characters, not k = " + std::to_string(k));
+        }
+        const size_t base = keys->size();
+        keys->resize(base + W, 0);
+        bool ok = true;
+        for (int j = 0; j < k; j++) {
+            uint64_t c;
+            switch (line[j]) {
+            case 'A': case 'a': c = 0; break;
+            case 'C': case 'c': c = 1; break;
+            case 'G': case 'g': c = 2; break;
+            case 'T': case 't': c = 3; break;
+            default: c = 0; ok = false;
+            }
+            const int bit = 2 * (k - 1 - j);
+            (*keys)[base + W - 1 - bit / 64] |= c << (bit % 64);
+        }
+        if (!ok) (*keys)[base] |= 1ULL << 63;
+        lines->push_back(line);
+    }
+    std::fclose(f);
+    return -1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     Args a;
     int prc = parse(argc, argv, &a);
     if (prc >= 0) return prc;
+    std::vector<std::string> qlines;  // --query: read and checked before anything else runs
+    std::vector<uint64_t> qkeys;
+    if (!a.query.empty() && a.k <= KC_MAX_K) {
+        const int qrc = read_queries(a.query, (int)a.k, &qlines, &qkeys);
+        if (qrc >= 0) return qrc;
+    }
 
     // ---- format detection (main.cpp:19-68)
     int fd = open(a.input.c_str(), O_RDONLY);
@@ -767,6 +835,25 @@ int main(int argc, char** argv) {
         if (kc_write(ctx, a.output.c_str()) != KC_OK) die("writing k-mers");
     }
     auto t2 = clk::now();
+    if (!a.histo.empty()) {  // extension: the abundance spectrum, every non-zero bin in ascending order
+        const uint32_t nb = a.mode == 0 ? 65537 : 16385;
+        std::vector<uint64_t> hist(nb);
+        if (kc_histogram(ctx, hist.data(), nb) != KC_OK) die("abundance histogram");
+        FILE* f = std::fopen(a.histo.c_str(), "w");
+        if (!f) { std::cerr << "cannot write " << a.histo << std::endl; kc_destroy(ctx); return 1; }
+        for (uint32_t v = 0; v < nb; v++)
+            if (hist[v]) std::fprintf(f, "%u %llu\n", v, (unsigned long long)hist[v]);
+        if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.histo << std::endl; kc_destroy(ctx); return 1; }
+    }
+    if (!a.query.empty()) {  // extension: the count of every query line, in order
+        std::vector<uint32_t> qcnt(qlines.size());
+        if (kc_lookup(ctx, qkeys.data(), qlines.size(), KC_KEYS_DUMP, qcnt.data()) != KC_OK) die("k-mer queries");
+        FILE* f = std::fopen(a.query_out.c_str(), "w");
+        if (!f) { std::cerr << "cannot write " << a.query_out << std::endl; kc_destroy(ctx); return 1; }
+        for (size_t i = 0; i < qlines.size(); i++) std::fprintf(f, "%s %u\n", qlines[i].c_str(), qcnt[i]);
+        if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.query_out << std::endl; kc_destroy(ctx); return 1; }
+    }
+    auto t3 = clk::now();
     std::cout << "Time used to build hash table: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() + (a.use_bf ? 0 : prep_us)
               << " microseconds\n";
@@ -776,6 +863,10 @@ int main(int argc, char** argv) {
                   << " stays the reference capacity)\n";
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
+    if (!a.histo.empty() || !a.query.empty())
+        std::cout << "Time used to query the hash table: "
+                  << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
+                  << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)") << "\n";
     std::cout << "Processed k-mers: " << stt.windows << " (inserted " << stt.inserted << ")\n";
     std::cout << "Main array slots used " << stt.distinct << " / " << ref_slots << "\n";
     std::cout << "Device table capacity: " << stt.table_slots << " slots\n";

@@ -404,6 +404,19 @@ hipError_t launch_compact_dump(int W, CompactView c, int k, uint64_t a, uint64_t
                                unsigned long long* stats, hipStream_t s);
 hipError_t launch_compact_lookup(int W, CompactView c, int k, const uint64_t* keys, uint64_t n, uint32_t* counts,
                                  hipStream_t s);
+// Queries of the counted table (kc_query_impl.h): T(c) of n keys of W words each -- layout
+// KC_KEYS_DUMP (the kc_dump key layout, either strand) or KC_KEYS_TABLE (table keys) -- into
+// counts (0 = absent), and the count-of-counts hist[min(T(c), n_bins - 1)] += 1 of every occupied
+// slot (hist zeroed by the caller).  Both only read the table.
+template <int W>
+struct QueryOps {
+    static hipError_t lookup(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
+                             uint32_t* counts, hipStream_t s);
+    static hipError_t histo(TableView t, int count_mode, uint32_t n_bins, unsigned long long* hist, hipStream_t s);
+};
+hipError_t launch_lookup(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
+                         uint32_t* counts, hipStream_t s);
+hipError_t launch_histo(TableView t, int count_mode, uint32_t n_bins, unsigned long long* hist, hipStream_t s);
 
 extern template struct WOps<1>;
 extern template struct WOps<2>;

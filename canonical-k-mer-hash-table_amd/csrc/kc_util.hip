@@ -1,6 +1,7 @@
 // kc_util.hip -- small device helpers: the device XXH64 of the reference-layout Bloom
 // passes (kc_common.h xxh64_u64) over host-given inputs (test hook), the chunk checksum of
-// the partition reuse, and the sharded Bloom filter's merge and filter-2 bit count.
+// the partition reuse, the sharded Bloom filter's merge and filter-2 bit count, and the
+// W-dispatch of the table queries (kc_query_w.hip).
 #include "kc_common.h"
 
 namespace kc {
@@ -150,6 +151,34 @@ __global__ void k_hold_overflow(DevCounters* ctr, int restore) {
 hipError_t launch_hold_overflow(DevCounters* ctr, int restore, hipStream_t s) {
     hipLaunchKernelGGL(k_hold_overflow, dim3(1), dim3(1), 0, s, ctr, restore);
     return hipGetLastError();
+}
+
+// W-dispatch of the table queries (kc_query_w.hip, one translation unit per key width)
+#define KC_DISPATCH_QW(W_, CALL)               \
+    switch (W_) {                              \
+    case 1: return QueryOps<1>::CALL;          \
+    case 2: return QueryOps<2>::CALL;          \
+    case 3: return QueryOps<3>::CALL;          \
+    case 4: return QueryOps<4>::CALL;          \
+    case 5: return QueryOps<5>::CALL;          \
+    case 6: return QueryOps<6>::CALL;          \
+    case 7: return QueryOps<7>::CALL;          \
+    case 8: return QueryOps<8>::CALL;          \
+    case 9: return QueryOps<9>::CALL;          \
+    case 10: return QueryOps<10>::CALL;        \
+    case 11: return QueryOps<11>::CALL;        \
+    case 12: return QueryOps<12>::CALL;        \
+    case 13: return QueryOps<13>::CALL;        \
+    case 14: return QueryOps<14>::CALL;        \
+    case 15: return QueryOps<15>::CALL;        \
+    default: return hipErrorInvalidValue;      \
+    }
+hipError_t launch_lookup(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
+                         uint32_t* counts, hipStream_t s) {
+    KC_DISPATCH_QW(t.W, lookup(t, k, count_mode, layout, keys, n, counts, s));
+}
+hipError_t launch_histo(TableView t, int count_mode, uint32_t n_bins, unsigned long long* hist, hipStream_t s) {
+    KC_DISPATCH_QW(t.W, histo(t, count_mode, n_bins, hist, s));
 }
 
 }  // namespace kc

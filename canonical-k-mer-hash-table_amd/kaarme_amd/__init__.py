@@ -38,6 +38,7 @@ ERRORS = {
     -7: "KC_ERR_UNSUPPORTED",
 }
 FMT_FASTA, FMT_FASTQ, FMT_PLAIN = 0, 1, 2
+KEYS_DUMP, KEYS_TABLE = 0, 1  # kc_lookup* key layouts (KC_KEYS_DUMP / KC_KEYS_TABLE)
 
 # Public C-ABI symbols (include/kc_api.h); tests check every one is exported.
 EXPORTS = (
@@ -51,6 +52,7 @@ EXPORTS = (
     "kc_bloom_estimate", "kc_compact", "kc_compact_dump", "kc_compact_lookup", "kc_compact_read", "kc_size_table",
     "kc_estimate_distinct_device", "kc_bloom_records_device", "kc_count_records_device", "kc_plan_chunks_device",
     "kc_output_digest", "kc_route_superkmers_device", "kc_count_packed_device", "kc_bloom_packed_device",
+    "kc_lookup_device", "kc_lookup", "kc_histogram",
 )
 
 
@@ -184,6 +186,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                   ctypes.POINTER(ctypes.c_double)]),
         "kc_compact_lookup": (I32, [P, P, U64, P]),
         "kc_compact_read": (I32, [P, P, U64, P, U64]),
+        "kc_lookup_device": (I32, [P, P, U64, I32, P, P]),
+        "kc_lookup": (I32, [P, P, U64, I32, P]),
+        "kc_histogram": (I32, [P, P, ctypes.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -269,6 +274,35 @@ def decode_records(records: np.ndarray, k: int) -> List[Tuple[str, int]]:
         chars[:, j] = lut[(recs[:, word] >> np.uint64(bit % 64)) & np.uint64(3)]
     strs = [bytes(r).decode() for r in chars]
     return list(zip(strs, (int(c) for c in recs[:, W])))
+
+
+def encode_kmers(strings: Sequence[str], k: int) -> np.ndarray:
+    """k-mer strings -> (n, W) uint64 keys in dump()'s key layout (the inverse of decode_records'
+    key part; the strand is kept as given).  A/C/G/T in upper or lower case; anything else, or a
+    string of another length, raises ValueError."""
+    W = words_for_k(k)
+    n = len(strings)
+    keys = np.zeros((n, W), dtype=np.uint64)
+    if n == 0:
+        return keys
+    for s_ in strings:
+        if len(s_) != k:
+            raise ValueError(f"not a {k}-mer: {s_!r}")
+    try:
+        raw = np.frombuffer("".join(strings).encode("ascii"), dtype=np.uint8).reshape(n, k)
+    except UnicodeEncodeError as e:
+        raise ValueError(f"not a nucleotide string: {e}") from None
+    lut = np.full(256, 255, dtype=np.uint8)
+    for i, ch in enumerate(b"ACGT"):
+        lut[ch] = lut[ch + 32] = i
+    codes = lut[raw]
+    if (codes > 3).any():
+        bad = int(np.argwhere(codes > 3)[0][0])
+        raise ValueError(f"not A/C/G/T: {strings[bad]!r}")
+    for j in range(k):
+        bit = 2 * (k - 1 - j)
+        keys[:, W - 1 - bit // 64] |= codes[:, j].astype(np.uint64) << np.uint64(bit % 64)
+    return keys
 
 
 @dataclass
@@ -556,6 +590,32 @@ class KmerCounter:
         out = np.zeros(k.shape[0], dtype=np.uint32)
         self._chk(self.lib.kc_compact_lookup(self._ctx, k.ctypes.data, k.shape[0], out.ctypes.data),
                   "kc_compact_lookup")
+        return out
+
+    # -- queries of the counted table (kc_lookup*, kc_histogram)
+    def lookup_device(self, keys_ptr: int, n: int, out_ptr: int, table_keys: bool = False, stream: int = 0):
+        """T(c) of n keys in device memory (W uint64 each: dump()'s key layout, either strand, or
+        route_device's table keys) into uint32 at out_ptr, 0 = absent; enqueued on `stream`, no wait."""
+        self._chk(self.lib.kc_lookup_device(self._ctx, ctypes.c_void_p(keys_ptr or None), n,
+                                            KEYS_TABLE if table_keys else KEYS_DUMP, ctypes.c_void_p(out_ptr or None),
+                                            ctypes.c_void_p(stream or None)), "kc_lookup_device")
+
+    def lookup(self, keys: np.ndarray, table_keys: bool = False) -> np.ndarray:
+        """T(c) of keys (n, W) uint64 (encode_kmers / dump()'s key layout, either strand; or table
+        keys); 0 = absent.  The minimum abundance is not applied."""
+        W = self.lib.kc_key_words(self._ctx)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, W)
+        out = np.zeros(k.shape[0], dtype=np.uint32)
+        self._chk(self.lib.kc_lookup(self._ctx, k.ctypes.data, k.shape[0], KEYS_TABLE if table_keys else KEYS_DUMP,
+                                     out.ctypes.data), "kc_lookup")
+        return out
+
+    def histogram(self, n_bins: int = 16385) -> np.ndarray:
+        """The count-of-counts: hist[v] = k-mers with T(c) == v, the last bin holding T(c) >= n_bins - 1."""
+        if not 0 <= n_bins < 2 ** 32:
+            raise KcError(-1, "kc_histogram: 2 <= n_bins <= 65537")
+        out = np.zeros(max(n_bins, 1), dtype=np.uint64)
+        self._chk(self.lib.kc_histogram(self._ctx, out.ctypes.data, n_bins), "kc_histogram")
         return out
 
     def compact_read(self, info: dict):

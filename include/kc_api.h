@@ -313,6 +313,39 @@ int kc_compact_dump(kc_ctx* ctx, uint64_t** records, uint64_t* n_records, uint64
 int kc_compact_lookup(kc_ctx* ctx, const uint64_t* keys, uint64_t n, uint32_t* counts);
 int kc_compact_read(kc_ctx* ctx, uint64_t* words, uint64_t n_words, uint64_t* second, uint64_t n_second_words);
 
+/* Queries of the counted table.  The reference has no counterpart: its table is only ever
+ * walked by the writers (kmer_hash_table.cpp:4318-4524); a caller that wants the count of a
+ * k-mer or the abundance spectrum reads its output file back.  Here the full-key table in HBM
+ * answers both.  A key's probe sequence ends at the first bucket with a free slot, so a lookup
+ * is normally one 128-byte bucket read, present or absent.
+ *   kc_lookup_device  T(c) of n_keys keys in device memory (kc_key_words() u64 each) into
+ *                     dev_counts (uint32, 0 = absent).  key_layout KC_KEYS_DUMP: the kc_dump key
+ *                     layout (word 0 most significant), either strand -- the k-mer is made
+ *                     canonical first; a key with a bit set above bit 2k - 1 is not a k-mer and
+ *                     answers 0.  KC_KEYS_TABLE: table keys as kc_route_device writes them (of a
+ *                     context of the same k), looked up as they are; word 0 == 0 answers 0.
+ *                     T(c) is kc_dump's: c mod 65536 for -m 0, min(c, 16383) otherwise; the
+ *                     minimum abundance -a is NOT applied (as in kc_compact_lookup).  Follows the
+ *                     *_device rule: enqueued on hip_stream after the work already queued there
+ *                     and after the context's own queued work (staged host chunks are flushed
+ *                     first); no host wait.
+ *   kc_lookup         the same for host arrays; waits for the answer.
+ *   kc_histogram      the count-of-counts of the whole table into hist[n_bins] (host array,
+ *                     2 <= n_bins <= 65537): hist[v] = k-mers with T(c) == v for v < n_bins - 1,
+ *                     hist[n_bins - 1] = k-mers with T(c) >= n_bins - 1 (hist[0]: only -m 0
+ *                     counts that wrapped to a multiple of 65536).  Not filtered by -a.  One
+ *                     sweep of the table; waits for the answer.
+ * Any table answers (Bloom-gated, filled by merges or kc_insert_*, counted over several
+ * batches); a table emptied by kc_reset or kc_clear_table answers 0 everywhere.  KC_ERR_STATE
+ * without a table (a Bloom context before kc_bloom_finalize); n_keys = 0 is KC_OK.  No counter
+ * of kc_stats changes. */
+#define KC_KEYS_DUMP  0   /* kc_dump key layout, either strand */
+#define KC_KEYS_TABLE 1   /* kc_route_device's table keys */
+int kc_lookup_device(kc_ctx* ctx, const uint64_t* dev_keys, uint64_t n_keys, int key_layout, uint32_t* dev_counts,
+                     void* hip_stream);
+int kc_lookup(kc_ctx* ctx, const uint64_t* keys, uint64_t n_keys, int key_layout, uint32_t* counts);
+int kc_histogram(kc_ctx* ctx, uint64_t* hist, uint32_t n_bins);
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);

@@ -18,6 +18,7 @@ wait
 for w in 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15; do
   $H $HIPFLAGS -DKC_W=$w -c $S/kc_count_w.hip -o $B/kc_count_w$w.o &
   $H $HIPFLAGS -DKC_W=$w -c $S/kc_compact_w.hip -o $B/kc_compact_w$w.o &
+  [ -f $S/kc_query_w.hip ] && $H $HIPFLAGS -DKC_W=$w -c $S/kc_query_w.hip -o $B/kc_query_w$w.o &
   if (( w % 4 == 0 )); then wait; fi
 done
 wait
