@@ -1,5 +1,5 @@
 // kc_internal.h -- declarations shared by the HIP kernels (kc_tokenize.hip, kc_count.hip) and the
-// host side of the C ABI (kc_api.cpp).  Not part of the public boundary
+// host side of the C ABI (kc_api*.cpp, kc_ctx.h).  Not part of the public boundary
 // (that is include/kc_api.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -137,14 +137,14 @@ struct PartBufs {
     uint32_t* own_hist;
     uint32_t own_parts;
     uint64_t own_nblk;
-    // deferred level 3 (kc_api.cpp run_batch): the level-2 segments of several batches of one image
+    // deferred level 3 (kc_api_pass.cpp run_batch): the level-2 segments of several batches of one image
     // stay in keys2 and one level-3 pass inserts them all, i.e. one sweep of the table per group of
     // batches instead of per batch.  Level 2 writes segment r * b2t + b2off + j of region r (b2t = 0:
     // B2 and no offset, one batch); the deferred level 3 runs with B2 = b2t.
     uint32_t b2t;
     uint32_t b2off;
     // a later batch of a deferred group: its skew-list entries go after the group's earlier
-    // batches' (the list is inserted once, after the group's level 3: kc_api.cpp run_deferred)
+    // batches' (the list is inserted once, after the group's level 3: kc_api_pass.cpp run_deferred)
     uint32_t keep_skew;
 };
 constexpr int R12_P1 = 1, R12_IN = 2, R12_OUT = 4, R12_L2 = 8;
@@ -243,7 +243,7 @@ hipError_t launch_count(PackedView sv, uint64_t sym_bound, int k, int mode, Tabl
 // phase (segmented layout): bit 0 = the single-pass levels (PH_MAIN), bit 1 = the batch's
 // tail: the skew list, the batch's bookkeeping and the exact pipeline behind the device
 // overflow gate (PH_TAIL).  The host may run the tail only when the main phase left a skew
-// list or an overflow (kc_api.cpp); with both empty every tail kernel is a no-op.
+// list or an overflow (kc_api_pass.cpp run_batch); with both empty every tail kernel is a no-op.
 constexpr int PH_MAIN = 1, PH_TAIL = 2, PH_ALL = 3;
 // Counting pass, deferred level 3 (segmented layout): the batch's levels 1-2 into its slot of the
 // group's level-2 segments (PartBufs b2t / b2off), and level 3 over the whole group (pb.B2 = b2t)
@@ -418,21 +418,29 @@ hipError_t launch_lookup(TableView t, int k, int count_mode, int layout, const u
                          uint32_t* counts, hipStream_t s);
 hipError_t launch_histo(TableView t, int count_mode, uint32_t n_bins, unsigned long long* hist, hipStream_t s);
 
-extern template struct WOps<1>;
-extern template struct WOps<2>;
-extern template struct WOps<3>;
-extern template struct WOps<4>;
-extern template struct WOps<5>;
-extern template struct WOps<6>;
-extern template struct WOps<7>;
-extern template struct WOps<8>;
-extern template struct CompactOps<1>;
-extern template struct CompactOps<2>;
-extern template struct CompactOps<3>;
-extern template struct CompactOps<4>;
-extern template struct CompactOps<5>;
-extern template struct CompactOps<6>;
-extern template struct CompactOps<7>;
-extern template struct CompactOps<8>;
+// Width dispatch of the launchers (kc_count.hip, kc_util.hip): Ops is WOps, CompactOps or QueryOps, whose
+// members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// list is needed beside it: the members have no definition in any other translation unit, so
+// nothing there can instantiate them implicitly.
+#define KC_DISPATCH(Ops, W_, CALL)             \
+    switch (W_) {                              \
+    case 1: return Ops<1>::CALL;               \
+    case 2: return Ops<2>::CALL;               \
+    case 3: return Ops<3>::CALL;               \
+    case 4: return Ops<4>::CALL;               \
+    case 5: return Ops<5>::CALL;               \
+    case 6: return Ops<6>::CALL;               \
+    case 7: return Ops<7>::CALL;               \
+    case 8: return Ops<8>::CALL;               \
+    case 9: return Ops<9>::CALL;               \
+    case 10: return Ops<10>::CALL;             \
+    case 11: return Ops<11>::CALL;             \
+    case 12: return Ops<12>::CALL;             \
+    case 13: return Ops<13>::CALL;             \
+    case 14: return Ops<14>::CALL;             \
+    case 15: return Ops<15>::CALL;             \
+    default: return hipErrorInvalidValue;      \
+    }
 
 }  // namespace kc

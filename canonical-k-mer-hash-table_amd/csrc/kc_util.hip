@@ -20,7 +20,7 @@ hipError_t launch_xxh64(const uint64_t* v, const uint64_t* seed, uint64_t n, uin
 
 // Checksum of the chunks' bytes: the sum over every aligned 8-byte word w overlapping a
 // chunk of fmix64(w's chunk bytes + its address * C), bytes outside the chunk masked.
-// Two passes over one image compare their sums (kc_api.cpp level-1 reuse).
+// Two passes over one image compare their sums (kc_api_pass.cpp count_reused).
 constexpr int CK_T = 256, CK_PER = 32;  // words per thread
 constexpr int CK_SLOTS = 64;            // partial sums (the caller adds them)
 __global__ __launch_bounds__(CK_T) void k_checksum(const uint8_t* __restrict__ src, const ChunkDesc* __restrict__ ch,
@@ -135,7 +135,7 @@ hipError_t launch_bloom_popcount2(const uint32_t* words, uint64_t n, int blocked
     return hipGetLastError();
 }
 
-// deferred level 3 (kc_api.cpp run_deferred): a batch whose segments overflowed holds its
+// deferred level 3 (kc_api_pass.cpp run_deferred): a batch whose segments overflowed holds its
 // part_overflow aside while the group's level 3 inserts the other batches (k_p3 skips on the
 // flag), then gets it back for its tail (the exact pipeline redoes that batch)
 __global__ void k_hold_overflow(DevCounters* ctr, int restore) {
@@ -154,31 +154,12 @@ hipError_t launch_hold_overflow(DevCounters* ctr, int restore, hipStream_t s) {
 }
 
 // W-dispatch of the table queries (kc_query_w.hip, one translation unit per key width)
-#define KC_DISPATCH_QW(W_, CALL)               \
-    switch (W_) {                              \
-    case 1: return QueryOps<1>::CALL;          \
-    case 2: return QueryOps<2>::CALL;          \
-    case 3: return QueryOps<3>::CALL;          \
-    case 4: return QueryOps<4>::CALL;          \
-    case 5: return QueryOps<5>::CALL;          \
-    case 6: return QueryOps<6>::CALL;          \
-    case 7: return QueryOps<7>::CALL;          \
-    case 8: return QueryOps<8>::CALL;          \
-    case 9: return QueryOps<9>::CALL;          \
-    case 10: return QueryOps<10>::CALL;        \
-    case 11: return QueryOps<11>::CALL;        \
-    case 12: return QueryOps<12>::CALL;        \
-    case 13: return QueryOps<13>::CALL;        \
-    case 14: return QueryOps<14>::CALL;        \
-    case 15: return QueryOps<15>::CALL;        \
-    default: return hipErrorInvalidValue;      \
-    }
 hipError_t launch_lookup(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
                          uint32_t* counts, hipStream_t s) {
-    KC_DISPATCH_QW(t.W, lookup(t, k, count_mode, layout, keys, n, counts, s));
+    KC_DISPATCH(QueryOps, t.W, lookup(t, k, count_mode, layout, keys, n, counts, s));
 }
 hipError_t launch_histo(TableView t, int count_mode, uint32_t n_bins, unsigned long long* hist, hipStream_t s) {
-    KC_DISPATCH_QW(t.W, histo(t, count_mode, n_bins, hist, s));
+    KC_DISPATCH(QueryOps, t.W, histo(t, count_mode, n_bins, hist, s));
 }
 
 }  // namespace kc

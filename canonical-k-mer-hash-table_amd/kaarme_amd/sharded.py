@@ -172,7 +172,7 @@ DEFAULT_BATCH = 256 << 20  # kc_api.cpp kDefaultBatch
 
 
 def batch_groups(chunks, batch_bytes: int):
-    """Split a chunk table into groups that each fit one staging batch (kc_api.cpp:
+    """Split a chunk table into groups that each fit one staging batch (kc_api_pass.cpp:
     chunks are placed at 4 KiB-aligned offsets of a batch_bytes stage)."""
     cap = (batch_bytes or DEFAULT_BATCH) // TILE * TILE
     groups, cur, used = [], [], 0

@@ -1,6 +1,6 @@
 """Deferred level 3: a counting pass over an image of several staging batches
 keeps the level-2 segments of a group of batches in HBM and inserts them with one level-3 pass
-(one sweep of the table per group instead of per batch; kc_api.cpp plan_deferral / run_deferred).
+(one sweep of the table per group instead of per batch; kc_api_pass.cpp plan_deferral / run_deferred).
 Results must equal the oracle's (the reference's restatement) and the undeferred pass's, for every
 key width and record format, for groups that do not divide the batch count, and when a batch of a
 group needs its tail (a skew list, or segments that overflow and send the batch to the exact

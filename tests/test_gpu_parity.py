@@ -139,6 +139,34 @@ def test_device_image_path_and_small_batches(name, k, args, golden_input, tmp_pa
             assert sorted_digest_lines(kc.lines()) == want, (chunk_size, batch)
 
 
+@pytest.mark.parametrize("name,k,batch", [("reads.txt", 31, 0), ("edge.fasta", 51, 0), ("edge.fasta", 51, 1 << 17)])
+def test_count_device_on_a_side_stream(name, k, batch, golden_input):
+    """kc_count_device on a caller's stream: the image is uploaded on a torch.cuda.Stream, the pass
+    (one batch, or several small ones) is issued on it with nothing waited for in between, and
+    the table read through the context afterwards is the null-stream pass's."""
+    torch = pytest.importorskip("torch")
+    path = golden_input(name)
+    image = open(path, "rb").read()
+    fmt = ka.detect_format(path, image[0])
+    chunks = ka.plan_chunks(image, k, fmt, 50000 if batch else 0)
+    cfg = ka.Config(k=k, mode=2, min_abundance=1, table_slots=1 << 20, batch_bytes=batch)
+    host = torch.frombuffer(bytearray(image), dtype=torch.uint8).pin_memory()
+    img = host.cuda()
+    with ka.KmerCounter(cfg) as kc:
+        kc.count_device(img.data_ptr(), chunks, fmt)
+        want, want_st = kc.lines(), kc.finish()
+    assert want
+    s = torch.cuda.Stream()
+    with ka.KmerCounter(cfg) as kc:
+        with torch.cuda.stream(s):
+            dev = torch.empty(len(image), dtype=torch.uint8, device="cuda")
+            dev.copy_(host, non_blocking=True)
+            kc.count_device(dev.data_ptr(), chunks, fmt, s.cuda_stream)
+        got, st = kc.lines(), kc.finish()
+    assert got == want
+    assert (st["windows"], st["distinct"]) == (want_st["windows"], want_st["distinct"])
+
+
 def test_synth_device_matches_cpu_generator(tmp_path):
     torch = pytest.importorskip("torch")
     lib = ka.load_library()
@@ -264,7 +292,7 @@ def test_segment_overflow_spills_or_falls_back(name, k, args, spill, src, golden
     spill=full: the spill list is too small too, so the device redoes the whole batch on
     the exact layout (behind the overflow gate).  Either way the result is the reference's.
     src=device: a device image, whose batch tail the host launches after reading the
-    overflow flag and the skew-list length (kc_api.cpp tail_needed)."""
+    overflow flag and the skew-list length (kc_api_pass.cpp tail_needed)."""
     monkeypatch.setenv("KC_INSERT_PATH", "partitioned")
     monkeypatch.setenv("KC_SEG_CAP", "8")
     monkeypatch.setenv("KC_SPILL_CAP", "64" if spill == "full" else str(1 << 24))
@@ -405,7 +433,7 @@ def _bloom_job_device(torch, img, chunks, k, count_img=None, count_chunks=None, 
 
 @pytest.mark.parametrize("change", ["none", "small_u", "bytes", "chunks", "batches"])
 def test_level1_reuse_only_on_the_same_input(change, monkeypatch):
-    """Partition reuse (kc_api.cpp): the counting pass starts from the Bloom pass's window
+    """Partition reuse (kc_api_pass.cpp count_reused): the counting pass starts from the Bloom pass's window
     partitions only for the same image, chunk table and bytes in one batch -- from level 2
     when the table's regions are unions of the fine bins (none), from level 1 when the table
     outgrew the bins sized from -u (small_u).  Bytes changed after the Bloom pass

@@ -9,6 +9,7 @@ runs at N > 1; tests/test_sharded.py covers the collective itself over gloo.
 import os
 import subprocess
 
+import numpy as np
 import pytest
 import torch
 
@@ -89,6 +90,52 @@ def test_insert_rejects_non_table_keys(monkeypatch, path):
     e.insert(keys, 5000, torch.cuda.current_stream().cuda_stream)
     with pytest.raises(ka.KcError, match="not table keys"):
         e.kc.finish()
+
+
+def _sorted_rows(d):
+    return d[np.lexsort(d.T[::-1])]
+
+
+@pytest.mark.parametrize("call", ["insert_keys_device", "insert_counts_device", "count_records_device"])
+@pytest.mark.parametrize("k,name", [(31, "reads.txt"), (51, "edge.fasta")])
+def test_inserts_on_a_side_stream(golden_input, k, name, call):
+    """The inserts of received keys and records on a caller's stream: the input arrives by a copy on a
+    torch.cuda.Stream, the insert is issued on it with nothing waited for in between, and the table
+    read through the context afterwards is the one the null-stream insert leaves."""
+    path = golden_input(name)
+    data, img = _image(path)
+    fmt = ka.detect_format(path, data[0])
+    chunks = ka.plan_chunks(data, k, fmt)
+    W = ka.words_for_k(k)
+    cfg = ka.Config(k=k, mode=2, table_slots=1 << 20, min_abundance=1, batch_bytes=len(data) + 4096 * (len(chunks) + 1))
+    with ka.KmerCounter(cfg) as src:
+        if call == "insert_keys_device":  # the windows' table keys
+            item = W
+            cap = sum((ln + 4095) // 4096 * 4096 for _, ln, _ in chunks) + len(chunks)
+            buf = torch.zeros(cap * item, dtype=torch.int64, device="cuda")
+            n = sum(src.route_device(img.data_ptr(), chunks, fmt, 1, buf.data_ptr(), cap))
+        else:  # the counted table's {key, count} records
+            item = W + 1
+            src.count_device(img.data_ptr(), chunks, fmt)
+            cap = src.finish()["distinct"]
+            buf = torch.zeros(cap * item, dtype=torch.int64, device="cuda")
+            n = sum(src.route_table_device(1, buf.data_ptr(), cap))
+        torch.cuda.synchronize()
+    assert n > 1000
+    host = buf[: n * item].cpu().pin_memory()
+
+    def table_after(stream):
+        with ka.KmerCounter(cfg) as kc:
+            with torch.cuda.stream(stream or torch.cuda.current_stream()):
+                dev = torch.empty(n * item, dtype=torch.int64, device="cuda")
+                dev.copy_(host, non_blocking=True)
+                getattr(kc, call)(dev.data_ptr(), n, stream.cuda_stream if stream else 0)
+            return _sorted_rows(kc.dump()), kc.finish()
+
+    want, want_st = table_after(None)
+    got, st = table_after(torch.cuda.Stream())
+    assert len(want) > 1000 and np.array_equal(got, want)
+    assert (st["inserted"], st["distinct"]) == (want_st["inserted"], want_st["distinct"])
 
 
 @pytest.mark.parametrize("merge", ["runs", "general", "shuffled", "runs_gaps"])

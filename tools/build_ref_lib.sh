@@ -13,7 +13,7 @@ $H $HIPFLAGS -c $S/kc_tokenize.hip -o $B/kc_tokenize.o &
 $H $HIPFLAGS -c $S/kc_util.hip -o $B/kc_util.o &
 $H $HIPFLAGS -c $S/kc_count.hip -o $B/kc_count.o &
 [ -f $S/kc_skm.hip ] && $H $HIPFLAGS -c $S/kc_skm.hip -o $B/kc_skm.o &
-$H $HIPFLAGS -x hip -c $S/kc_api.cpp -o $B/kc_api.o &
+for f in $S/kc_api*.cpp; do $H $HIPFLAGS -x hip -c $f -o $B/$(basename $f .cpp).o & done
 wait
 for w in 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15; do
   $H $HIPFLAGS -DKC_W=$w -c $S/kc_count_w.hip -o $B/kc_count_w$w.o &
