@@ -509,6 +509,7 @@ void kc_destroy(kc_ctx* c) {
     for (auto e : c->h_free)
         if (e) hipEventDestroy(e);
     if (c->xev) hipEventDestroy(c->xev);
+    if (c->seq_ev) hipEventDestroy(c->seq_ev);
     for (auto e : c->aev)
         if (e) hipEventDestroy(e);
     if (c->aux) hipStreamDestroy(c->aux);

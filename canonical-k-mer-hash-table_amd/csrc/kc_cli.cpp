@@ -61,6 +61,12 @@ struct Args {
     // extensions that query the counted table (kc_histogram / kc_lookup): --histo FILE writes the
     // abundance spectrum, --query FILE --query-out FILE answers one k-mer per line
     std::string histo, query, query_out;
+    // --coverage FILE --coverage-out FILE [--coverage-min N]: per-record statistics of the k-mer
+    // counts of another file's sequences (kc_seq_stats); N (a k-mer is solid from this count on)
+    // defaults to the -a value
+    std::string coverage, coverage_out;
+    unsigned long long coverage_min = 0;
+    bool coverage_min_set = false;
 };
 
 void usage(const char* prog) {
@@ -82,7 +88,11 @@ void usage(const char* prog) {
                  "                              size next_prime3mod4(-s) (the device table keeps 25 % headroom)\n"
                  "  --histo FILE                write the abundance spectrum \"<count> <k-mers>\" (not filtered by -a)\n"
                  "  --query FILE                k-mers to look up, one per line (either strand, any case)\n"
-                 "  --query-out FILE            their counts \"<k-mer> <count>\" (0 = absent); needed with --query\n\n"
+                 "  --query-out FILE            their counts \"<k-mer> <count>\" (0 = absent); needed with --query\n"
+                 "  --coverage FILE             sequences (FASTA, FASTQ or one per line) whose k-mers to look up\n"
+                 "  --coverage-out FILE         per record, tab-separated: name length windows present solid min\n"
+                 "                              median max sum (of its k-mers' counts); needed with --coverage\n"
+                 "  --coverage-min UINT         a k-mer is solid from this count on (def. the -a value)\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -257,6 +267,15 @@ int parse(int argc, char** argv, Args* a) {
                 a->query = v;
             } else if (o == "--query-out") {
                 a->query_out = v;
+            } else if (o == "--coverage") {
+                a->coverage = v;
+            } else if (o == "--coverage-out") {
+                a->coverage_out = v;
+            } else if (o == "--coverage-min") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                a->coverage_min = u;
+                a->coverage_min_set = true;
             } else if (o == "--readers") {
                 if (!parse_int(v, &si) || si < 1 || si > 16) return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 a->readers = (unsigned)si;
@@ -283,6 +302,12 @@ int parse(int argc, char** argv, Args* a) {
     if (a->fpr_set && !a->use_bf) return cli_error(kRequires, "--bfilter-fpr requires --use-bfilter");
     if (!a->query.empty() && a->query_out.empty()) return cli_error(kRequires, "--query requires --query-out");
     if (a->query.empty() && !a->query_out.empty()) return cli_error(kRequires, "--query-out requires --query");
+    if (!a->coverage.empty() && a->coverage_out.empty())
+        return cli_error(kRequires, "--coverage requires --coverage-out");
+    if (a->coverage.empty() && !a->coverage_out.empty())
+        return cli_error(kRequires, "--coverage-out requires --coverage");
+    if (a->coverage_min_set && a->coverage.empty()) return cli_error(kRequires, "--coverage-min requires --coverage");
+    if (!a->coverage_min_set) a->coverage_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
     return -1;
 }
 
@@ -492,6 +517,93 @@ int read_queries(const std::string& path, int k, std::vector<std::string>* lines
     return -1;
 }
 
+// --coverage FILE: the records of a FASTA (multi-line records joined), FASTQ (four-line records)
+// or one-sequence-per-line file, the format detected as the input's is (extension and first byte;
+// not gzip).  The sequences go into one text, a newline after each -- a break byte, so no k-mer
+// spans two records -- with offsets[i] the start of record i (kc_seq_stats).  A record's name is
+// its header's first whitespace-delimited token without the '>' or '@'; in a plain file its
+// 1-based line number.  Returns -1 on success, else the exit code.
+struct Coverage {
+    std::string text;
+    std::vector<uint64_t> offsets;
+    std::vector<std::string> names;
+    std::vector<uint64_t> lengths;
+};
+int read_coverage(const std::string& path, Coverage* cv) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return cli_error(kValidation, "--coverage: File does not exist: " + path);
+    std::string data;
+    char buf[1 << 16];
+    size_t got;
+    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) data.append(buf, got);
+    std::fclose(f);
+    if (data.size() >= 2 && (unsigned char)data[0] == 0x1f && (unsigned char)data[1] == 0x8b)
+        return cli_error(kValidation, "--coverage: gzip input is not supported: " + path);
+    const std::string ext = ext_of(path);
+    const unsigned char sym = data.empty() ? 0 : (unsigned char)data[0];
+    int fmt;
+    bool ill;
+    if (ext == ".fasta" || ext == ".fa") { fmt = KC_FMT_FASTA; ill = sym != '>'; }
+    else if (ext == ".fastq" || ext == ".fq") { fmt = KC_FMT_FASTQ; ill = sym != '@'; }
+    else { fmt = KC_FMT_PLAIN; ill = !(sym && std::strchr("actgACGT", sym)); }
+    if (ill) return cli_error(kValidation, "--coverage: Input file " + path + " is ill-formed");
+    auto name_of = [](const std::string& header) {
+        size_t e = 1;
+        while (e < header.size() && !std::isspace((unsigned char)header[e])) e++;
+        return header.substr(1, e - 1);
+    };
+    auto open_record = [&](const std::string& name) {
+        cv->names.push_back(name);
+        cv->offsets.push_back(cv->text.size());
+        cv->lengths.push_back(0);
+    };
+    auto add_sequence = [&](const std::string& line) {
+        cv->text += line;
+        cv->lengths.back() += line.size();
+    };
+    auto close_record = [&] { cv->text.push_back('\n'); };
+    unsigned long long lineno = 0;
+    int phase = 0;  // FASTQ: the line of the record (0 header, 1 sequence, 2 '+', 3 qualities)
+    bool in_record = false;
+    for (size_t pos = 0; pos < data.size();) {
+        size_t nl = data.find('\n', pos);
+        if (nl == std::string::npos) nl = data.size();
+        std::string line = data.substr(pos, nl - pos);
+        pos = nl + 1;
+        lineno++;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (fmt == KC_FMT_FASTA) {
+            if (!line.empty() && line[0] == '>') {
+                if (in_record) close_record();
+                open_record(name_of(line));
+                in_record = true;
+            } else if (in_record) {
+                add_sequence(line);
+            }
+        } else if (fmt == KC_FMT_FASTQ) {
+            if (phase == 0 && line.empty()) continue;
+            if (phase == 0) {
+                if (line[0] != '@')
+                    return cli_error(kValidation, "--coverage: line " + std::to_string(lineno) + " of " + path +
+                                                      " is not a FASTQ header");
+                open_record(name_of(line));
+            } else if (phase == 1) {
+                add_sequence(line);
+                close_record();
+            }
+            phase = (phase + 1) & 3;
+        } else if (!line.empty()) {
+            open_record(std::to_string(lineno));
+            add_sequence(line);
+            close_record();
+        }
+    }
+    if (fmt == KC_FMT_FASTA && in_record) close_record();
+    if (fmt == KC_FMT_FASTQ && phase == 1) close_record();  // (a header with nothing after it)
+    cv->offsets.push_back(cv->text.size());
+    return -1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -503,6 +615,11 @@ int main(int argc, char** argv) {
     if (!a.query.empty() && a.k <= KC_MAX_K) {
         const int qrc = read_queries(a.query, (int)a.k, &qlines, &qkeys);
         if (qrc >= 0) return qrc;
+    }
+    Coverage cov;  // --coverage: read and checked before anything else runs, too
+    if (!a.coverage.empty()) {
+        const int crc = read_coverage(a.coverage, &cov);
+        if (crc >= 0) return crc;
     }
 
     // ---- format detection (main.cpp:19-68)
@@ -853,6 +970,19 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < qlines.size(); i++) std::fprintf(f, "%s %u\n", qlines[i].c_str(), qcnt[i]);
         if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.query_out << std::endl; kc_destroy(ctx); return 1; }
     }
+    if (!a.coverage.empty()) {  // extension: the k-mer count statistics of every record, in order
+        std::vector<kc_seq_stat> cst(cov.names.size());
+        if (kc_seq_stats(ctx, (const uint8_t*)cov.text.data(), cov.text.size(), cov.offsets.data(), cov.names.size(),
+                         (uint32_t)a.coverage_min, cst.data()) != KC_OK)
+            die("sequence coverage");
+        FILE* f = std::fopen(a.coverage_out.c_str(), "w");
+        if (!f) { std::cerr << "cannot write " << a.coverage_out << std::endl; kc_destroy(ctx); return 1; }
+        for (size_t i = 0; i < cst.size(); i++)
+            std::fprintf(f, "%s\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%llu\n", cov.names[i].c_str(),
+                         (unsigned long long)cov.lengths[i], cst[i].windows, cst[i].present, cst[i].solid, cst[i].min,
+                         cst[i].median, cst[i].max, (unsigned long long)cst[i].sum);
+        if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.coverage_out << std::endl; kc_destroy(ctx); return 1; }
+    }
     auto t3 = clk::now();
     std::cout << "Time used to build hash table: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() + (a.use_bf ? 0 : prep_us)
@@ -863,10 +993,11 @@ int main(int argc, char** argv) {
                   << " stays the reference capacity)\n";
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
-    if (!a.histo.empty() || !a.query.empty())
+    if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty())
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
-                  << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)") << "\n";
+                  << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")
+                  << (a.coverage.empty() ? "" : " (" + std::to_string(cov.names.size()) + " coverage records)") << "\n";
     std::cout << "Processed k-mers: " << stt.windows << " (inserted " << stt.inserted << ")\n";
     std::cout << "Main array slots used " << stt.distinct << " / " << ref_slots << "\n";
     std::cout << "Device table capacity: " << stt.table_slots << " slots\n";

@@ -231,6 +231,16 @@ struct kc_ctx {
     uint64_t reuse_hits = 0;          // counting passes that reused (kc_stats.reused_passes)
     int reuse_last_level = 0;         // the level the last reused pass started from (kc_stats.reuse_level)
 
+    // sequence queries (kc_api_seq.cpp): one pass's packed stream and per-position counts, the
+    // sequences' offsets followed by the ids of the long ones (device copy and the pinned block it is
+    // copied from; seq_ev: that copy has read the pinned block)
+    DevBuf<uint64_t> d_seq_pk;
+    DevBuf<uint32_t> d_seq_bk;
+    DevBuf<uint32_t> d_seq_cnt;
+    DevBuf<uint64_t> d_seq_off;
+    PinnedBuf<uint64_t> h_seq_off;
+    hipEvent_t seq_ev = nullptr;
+
     uint64_t n_chunks = 0, n_bytes = 0;
 
     // Deferred level 3 (device_pass / run_deferred): a counting pass over an image of several

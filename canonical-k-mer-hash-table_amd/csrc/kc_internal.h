@@ -417,10 +417,31 @@ struct QueryOps {
 hipError_t launch_lookup(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
                          uint32_t* counts, hipStream_t s);
 hipError_t launch_histo(TableView t, int count_mode, uint32_t n_bins, unsigned long long* hist, hipStream_t s);
+// Sequence queries of the counted table (kc_seq.hip, kc_seq_impl.h).  launch_seq_pack: n text bytes
+// -> a packed stream with symbol p = byte p (every non-ACGT byte a break) of seq_pack_words(n)
+// words, the bytes past n breaks.  counts: counts[p], p < n_pos, = T(c) of the window starting at
+// symbol p, or KC_NO_KMER when it holds a break or ends past n_sym; no key goes through HBM.
+// launch_seq_reduce: the kc_seq_stat of sequences i0 .. i1 - 1 (bytes [off[i], off[i + 1]) of the
+// text, off in device memory) from the counts of the text from byte `base` on; sequences of more
+// than SEQ_WAVE_MAX bytes are named in long_ids (device, n_long of them) and take a workgroup
+// each, the others a wave.
+constexpr uint32_t SEQ_WAVE_MAX = 2048;
+inline uint64_t seq_pack_words(uint64_t n) { return (n + 31) / 32 + 1; }
+template <int W>
+struct SeqOps {
+    static hipError_t counts(TableView t, PackedView sv, int k, int count_mode, uint64_t n_pos, uint64_t n_sym,
+                             uint32_t* counts, hipStream_t s);
+};
+hipError_t launch_seq_pack(const uint8_t* text, uint64_t n, PackedView sv, hipStream_t s);
+hipError_t launch_seq_counts(TableView t, PackedView sv, int k, int count_mode, uint64_t n_pos, uint64_t n_sym,
+                             uint32_t* counts, hipStream_t s);
+hipError_t launch_seq_reduce(const uint32_t* counts, uint64_t base, const uint64_t* off, uint64_t i0, uint64_t i1,
+                             const uint64_t* long_ids, uint64_t n_long, int k, uint32_t solid_min, kc_seq_stat* stats,
+                             hipStream_t s);
 
-// Width dispatch of the launchers (kc_count.hip, kc_util.hip): Ops is WOps, CompactOps or QueryOps, whose
+// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip): Ops is WOps, CompactOps, QueryOps or SeqOps, whose
 // members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

@@ -39,6 +39,10 @@ ERRORS = {
 }
 FMT_FASTA, FMT_FASTQ, FMT_PLAIN = 0, 1, 2
 KEYS_DUMP, KEYS_TABLE = 0, 1  # kc_lookup* key layouts (KC_KEYS_DUMP / KC_KEYS_TABLE)
+NO_KMER = 0xFFFFFFFF  # kc_text_counts*: no k-mer starts at this position (KC_NO_KMER)
+# kc_seq_stat (include/kc_api.h), 32 bytes
+SEQ_STAT_DTYPE = np.dtype([("windows", "<u4"), ("present", "<u4"), ("solid", "<u4"), ("min", "<u4"),
+                           ("median", "<u4"), ("max", "<u4"), ("sum", "<u8")])
 
 # Public C-ABI symbols (include/kc_api.h); tests check every one is exported.
 EXPORTS = (
@@ -53,6 +57,7 @@ EXPORTS = (
     "kc_estimate_distinct_device", "kc_bloom_records_device", "kc_count_records_device", "kc_plan_chunks_device",
     "kc_output_digest", "kc_route_superkmers_device", "kc_count_packed_device", "kc_bloom_packed_device",
     "kc_lookup_device", "kc_lookup", "kc_histogram",
+    "kc_text_counts_device", "kc_text_counts", "kc_seq_stats_device", "kc_seq_stats",
 )
 
 
@@ -189,6 +194,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_lookup_device": (I32, [P, P, U64, I32, P, P]),
         "kc_lookup": (I32, [P, P, U64, I32, P]),
         "kc_histogram": (I32, [P, P, ctypes.c_uint32]),
+        "kc_text_counts_device": (I32, [P, P, U64, P, P]),
+        "kc_text_counts": (I32, [P, P, U64, P]),
+        "kc_seq_stats_device": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P, P]),
+        "kc_seq_stats": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -303,6 +312,17 @@ def encode_kmers(strings: Sequence[str], k: int) -> np.ndarray:
         bit = 2 * (k - 1 - j)
         keys[:, W - 1 - bit // 64] |= codes[:, j].astype(np.uint64) << np.uint64(bit % 64)
     return keys
+
+
+def pack_sequences(seqs: Sequence) -> Tuple[bytes, np.ndarray]:
+    """Sequences (str or bytes) -> (text, offsets) for seq_stats / kc_seq_stats: the sequences joined
+    with one newline each (a break byte), offsets[i] .. offsets[i + 1] - 1 being sequence i and its
+    newline; uint64 offsets of len(seqs) + 1 entries, so the last is len(text)."""
+    parts = [s_.encode("ascii") if isinstance(s_, str) else bytes(s_) for s_ in seqs]
+    offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+    if parts:
+        offsets[1:] = np.cumsum([len(p_) + 1 for p_ in parts], dtype=np.uint64)
+    return b"".join(p_ + b"\n" for p_ in parts), offsets
 
 
 @dataclass
@@ -616,6 +636,43 @@ class KmerCounter:
             raise KcError(-1, "kc_histogram: 2 <= n_bins <= 65537")
         out = np.zeros(max(n_bins, 1), dtype=np.uint64)
         self._chk(self.lib.kc_histogram(self._ctx, out.ctypes.data, n_bins), "kc_histogram")
+        return out
+
+    # -- sequence queries (kc_text_counts*, kc_seq_stats*)
+    def text_counts_device(self, text_ptr: int, n: int, out_ptr: int, stream: int = 0):
+        """T(c) of the k-mer starting at each of the n bytes of a text in device memory (A/C/G/T in
+        either case are bases, every other byte a break) into n uint32 at out_ptr; NO_KMER where no
+        k-mer starts; enqueued on `stream`, no wait."""
+        self._chk(self.lib.kc_text_counts_device(self._ctx, ctypes.c_void_p(text_ptr or None), n,
+                                                 ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)),
+                  "kc_text_counts_device")
+
+    def text_counts(self, text: bytes) -> np.ndarray:
+        """T(c) of the k-mer starting at every byte of `text` (uint32, NO_KMER where none starts)."""
+        text = bytes(text)
+        out = np.zeros(len(text), dtype=np.uint32)
+        self._chk(self.lib.kc_text_counts(self._ctx, text, len(text), out.ctypes.data), "kc_text_counts")
+        return out
+
+    def seq_stats_device(self, text_ptr: int, n_bytes: int, offsets, out_ptr: int, solid_min: int = 1,
+                         stream: int = 0):
+        """Per-sequence statistics of a text in device memory: sequence i is the bytes
+        [offsets[i], offsets[i + 1]) (host offsets, one more than sequences); SEQ_STAT_DTYPE records
+        into device memory at out_ptr; enqueued on `stream`."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_seqs = max(len(off) - 1, 0)
+        self._chk(self.lib.kc_seq_stats_device(self._ctx, ctypes.c_void_p(text_ptr or None), n_bytes, off.ctypes.data,
+                                               n_seqs, solid_min, ctypes.c_void_p(out_ptr or None),
+                                               ctypes.c_void_p(stream or None)), "kc_seq_stats_device")
+
+    def seq_stats(self, seqs: Sequence, solid_min: int = 1) -> np.ndarray:
+        """Statistics of the k-mer counts of each sequence (str or bytes): a SEQ_STAT_DTYPE array with
+        windows, present (T(c) >= 1), solid (T(c) >= solid_min), min, median (lower), max and sum."""
+        text, off = pack_sequences(seqs)  # (a sequence's newline is a break: no window holds it)
+        out = np.zeros(len(off) - 1, dtype=SEQ_STAT_DTYPE)
+        if len(out):
+            self._chk(self.lib.kc_seq_stats(self._ctx, text, len(text), off.ctypes.data, len(out), solid_min,
+                                            out.ctypes.data), "kc_seq_stats")
         return out
 
     def compact_read(self, info: dict):

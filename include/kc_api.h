@@ -346,6 +346,54 @@ int kc_lookup_device(kc_ctx* ctx, const uint64_t* dev_keys, uint64_t n_keys, int
 int kc_lookup(kc_ctx* ctx, const uint64_t* keys, uint64_t n_keys, int key_layout, uint32_t* counts);
 int kc_histogram(kc_ctx* ctx, uint64_t* hist, uint32_t n_bins);
 
+/* Sequence queries of the counted table: how abundant are the k-mers of this read, contig or
+ * gene in what was counted.  One fused pass goes from text to a count per position -- no key is
+ * written to or read back from HBM -- and a segmented reduction gives per-sequence statistics.
+ *   kc_text_counts_device  The text is ONE byte stream of n_bytes in device memory, at any byte
+ *                     address.  A, C, G, T in either case are bases; every other byte (N, a
+ *                     newline, '>', ...) is a break.  dev_counts[p] (uint32, all n_bytes entries
+ *                     are written) is T(c) of the canonical k-mer of text[p .. p + k) when all k
+ *                     bytes are bases and p + k <= n_bytes, and KC_NO_KMER otherwise.  T(c) is
+ *                     kc_lookup's: c mod 65536 for -m 0, min(c, 16383) otherwise, 0 if absent;
+ *                     the minimum abundance -a is NOT applied.  Nothing is parsed: headers and
+ *                     quality lines are the caller's to leave out, and sequence boundaries are
+ *                     whatever break bytes the caller put between sequences (two sequences joined
+ *                     with no break byte between them share the k - 1 windows across the joint).
+ *   kc_text_counts    the same for host arrays; waits for the answer.
+ *   kc_seq_stats_device  per-sequence statistics of the same kind of text.  offsets is a HOST
+ *                     array of n_seqs + 1 non-decreasing byte offsets with offsets[n_seqs] <=
+ *                     n_bytes (like the kc_chunk table beside a device image; copied before the
+ *                     call returns); sequence i is the bytes [offsets[i], offsets[i + 1]).  Its
+ *                     windows are the positions p in that range with p + k <= offsets[i + 1] and a
+ *                     valid k-mer at p, so a window never spans two sequences, even when they are
+ *                     adjacent with no break byte.  dev_stats[i] (device memory, n_seqs entries)
+ *                     receives the kc_seq_stat below.  The per-position counts are scratch of the
+ *                     context: the text runs in passes cut at sequence boundaries of at most the
+ *                     context's staging batch (kc_config.batch_bytes) each, a longer single
+ *                     sequence being a pass of its own length (4.4 bytes of scratch per byte).
+ *                     Offsets that decrease or pass n_bytes: KC_ERR_ARG.
+ *   kc_seq_stats      the same for a host text and a host result array; waits for the answer.
+ * The *_device forms follow the *_device rule as kc_lookup_device does (enqueued on hip_stream
+ * after the work queued there and after the context's own; no host wait beyond an earlier call's
+ * offsets copy).  Any table answers, an emptied one 0 everywhere; KC_ERR_STATE without a table;
+ * n_bytes = 0 and n_seqs = 0 are KC_OK; no counter of kc_stats changes. */
+#define KC_NO_KMER 0xFFFFFFFFu      /* no k-mer starts at this position */
+typedef struct {                    /* 32 bytes */
+    uint32_t windows;   /* positions of the sequence where a k-mer starts (k bases, inside the sequence) */
+    uint32_t present;   /* of those, T(c) >= 1 */
+    uint32_t solid;     /* of those, T(c) >= solid_min */
+    uint32_t min, median, max;  /* of T(c) over the windows, absent k-mers counting as 0; the median is
+                                   element (windows - 1) / 2 of the sorted values (the lower median) */
+    uint64_t sum;       /* sum of T(c) over the windows */
+} kc_seq_stat;          /* windows == 0: every field 0 */
+int kc_text_counts_device(kc_ctx* ctx, const uint8_t* dev_text, uint64_t n_bytes, uint32_t* dev_counts,
+                          void* hip_stream);
+int kc_text_counts(kc_ctx* ctx, const uint8_t* text, uint64_t n_bytes, uint32_t* counts);
+int kc_seq_stats_device(kc_ctx* ctx, const uint8_t* dev_text, uint64_t n_bytes, const uint64_t* offsets,
+                        uint64_t n_seqs, uint32_t solid_min, kc_seq_stat* dev_stats, void* hip_stream);
+int kc_seq_stats(kc_ctx* ctx, const uint8_t* text, uint64_t n_bytes, const uint64_t* offsets, uint64_t n_seqs,
+                 uint32_t solid_min, kc_seq_stat* stats);
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
