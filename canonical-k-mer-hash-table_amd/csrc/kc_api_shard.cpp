@@ -143,26 +143,7 @@ int kc_route_table_device(kc_ctx* c, uint32_t nshards, uint64_t* dev_out, uint64
 
 }  // extern "C"
 
-// What the record / key inserts share, on the caller's stream (joined here unless the caller has):
-// `size` prepares the partition buffers (or the table), before the profiling bracket opens or
-// (prof_first) after it; `work` is the launch the bracket times; then the table's -- or (bloom) the
-// filter's -- freshness flags.
-template <class Size, class Work>
-static int insert_on(kc_ctx* c, StreamScope& on, bool bloom, bool prof_first, Size size, Work work) {
-    int rc = on.join();
-    if (rc) return rc;
-    if (prof_first && (rc = on.profile())) return rc;
-    if ((rc = size())) return rc;
-    if (!prof_first && (rc = on.profile())) return rc;
-    if ((rc = work())) return rc;
-    if (bloom) {
-        c->bloom_fresh = false;
-    } else {
-        own_after_write(c, false, false);
-        c->table_fresh = c->table_zero_pending = false;
-    }
-    return on.finish();
-}
+// (what the record / key inserts below share: insert_on, kc_ctx.h)
 
 extern "C" {
 

@@ -67,7 +67,16 @@ struct Args {
     std::string coverage, coverage_out;
     unsigned long long coverage_min = 0;
     bool coverage_min_set = false;
+    // --op NAME --with FILE2 [--a-min/--a-max/--b-min/--b-max N]: FILE2 is counted like INPUT into a
+    // second table and the output is the result of the table operation (kc_table_op) on the two
+    std::string op_name, with;
+    int op = -1;
+    unsigned long long a_min = 0, a_max = 0, b_min = 0, b_max = 0;
+    bool range_set = false;
 };
+
+const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
+                                "counts-subtract", "union-sum", "union-max"};  // KC_OP_* order
 
 void usage(const char* prog) {
     std::cout << "Space-efficient k-mer counter\n"
@@ -92,7 +101,12 @@ void usage(const char* prog) {
                  "  --coverage FILE             sequences (FASTA, FASTQ or one per line) whose k-mers to look up\n"
                  "  --coverage-out FILE         per record, tab-separated: name length windows present solid min\n"
                  "                              median max sum (of its k-mers' counts); needed with --coverage\n"
-                 "  --coverage-min UINT         a k-mer is solid from this count on (def. the -a value)\n\n"
+                 "  --coverage-min UINT         a k-mer is solid from this count on (def. the -a value)\n"
+                 "  --op NAME                   output a table operation on INPUT (a) and the --with file (b): intersect-min,\n"
+                 "                              intersect-sum, intersect-left, subtract, counts-subtract, union-sum, union-max\n"
+                 "  --with FILE                 the second input, counted with the same options; needed with --op\n"
+                 "  --a-min,--a-max,--b-min,--b-max UINT\n"
+                 "                              a k-mer takes part when its count is in its file's range (def. 1 and up)\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -276,6 +290,20 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 a->coverage_min = u;
                 a->coverage_min_set = true;
+            } else if (o == "--op") {
+                a->op_name = v;
+                for (int q = 0; q < 7; q++)
+                    if (v == kOpNames[q]) a->op = q;
+                if (a->op < 0)
+                    return cli_error(kValidation, o + ": Value " + v + " not in {intersect-min, intersect-sum, "
+                                                  "intersect-left, subtract, counts-subtract, union-sum, union-max}");
+            } else if (o == "--with") {
+                a->with = v;
+            } else if (o == "--a-min" || o == "--a-max" || o == "--b-min" || o == "--b-max") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                (o == "--a-min" ? a->a_min : o == "--a-max" ? a->a_max : o == "--b-min" ? a->b_min : a->b_max) = u;
+                a->range_set = true;
             } else if (o == "--readers") {
                 if (!parse_int(v, &si) || si < 1 || si > 16) return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 a->readers = (unsigned)si;
@@ -308,6 +336,13 @@ int parse(int argc, char** argv, Args* a) {
         return cli_error(kRequires, "--coverage-out requires --coverage");
     if (a->coverage_min_set && a->coverage.empty()) return cli_error(kRequires, "--coverage-min requires --coverage");
     if (!a->coverage_min_set) a->coverage_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
+    if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
+    if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
+    if ((a->a_max && a->a_min > a->a_max) || (a->b_max && a->b_min > a->b_max))
+        return cli_error(kValidation, "--a-min/--b-min: a minimum above its maximum");
+    if (!a->with.empty() && (stat(a->with.c_str(), &st) != 0 || S_ISDIR(st.st_mode)))
+        return cli_error(kValidation, "--with: File does not exist: " + a->with);
     return -1;
 }
 
@@ -602,6 +637,77 @@ int read_coverage(const std::string& path, Coverage* cv) {
     if (fmt == KC_FMT_FASTQ && phase == 1) close_record();  // (a header with nothing after it)
     cv->offsets.push_back(cv->text.size());
     return -1;
+}
+
+// --with FILE2: the second operand of --op, counted like INPUT -- the same k, -m, -s or -b -u -f, the
+// format detected the same way, gzip inflated -- into a context of its own, through staged host
+// chunks.  Returns nullptr after it has printed what failed.
+kc_ctx* count_with(const Args& a, kc_config cfg) {
+    unsigned char magic[2] = {0, 0};
+    if (FILE* f = std::fopen(a.with.c_str(), "rb")) {
+        size_t r = std::fread(magic, 1, 2, f);
+        (void)r;
+        std::fclose(f);
+    }
+    const bool gz = magic[0] == 0x1f && magic[1] == 0x8b;
+    gzFile g = gzopen(a.with.c_str(), "rb");  // (an uncompressed file is read as it is)
+    if (!g) { std::cerr << "cannot open " << a.with << "\n"; return nullptr; }
+    gzbuffer(g, 1 << 20);
+    std::vector<uint8_t> img, tmp(1 << 22);
+    int n;
+    while ((n = gzread(g, tmp.data(), (unsigned)tmp.size())) > 0) img.insert(img.end(), tmp.begin(), tmp.begin() + n);
+    int zerr = Z_OK;
+    const char* msg = gzerror(g, &zerr);
+    if (n < 0 || (zerr != Z_OK && zerr != Z_STREAM_END)) {
+        std::cerr << "--with input " << a.with << " is corrupt or truncated: " << (msg ? msg : "") << std::endl;
+        gzclose(g);
+        return nullptr;
+    }
+    gzclose(g);
+    std::string ext_path = a.with;
+    if (gz)
+        while (ext_of(ext_path) == ".gz") ext_path = ext_path.substr(0, ext_path.size() - 3);
+    const std::string ext = ext_of(ext_path);
+    const unsigned char sym = img.empty() ? 0 : img[0];
+    int fmt;
+    bool ill;
+    if (ext == ".fasta" || ext == ".fa") { fmt = KC_FMT_FASTA; ill = sym != '>'; }
+    else if (ext == ".fastq" || ext == ".fq") { fmt = KC_FMT_FASTQ; ill = sym != '@'; }
+    else { fmt = KC_FMT_PLAIN; ill = !(sym && std::strchr("actgACGT", sym)); }
+    if (ill) { std::cerr << "Input file " << a.with << " is ill-formed" << std::endl; return nullptr; }
+    kc_chunk* chunks = nullptr;
+    uint64_t nch = 0;
+    if (kc_plan_chunks(img.data(), img.size(), cfg.k, 0, fmt, &chunks, &nch) != KC_OK) {
+        std::cerr << "chunk planning of " << a.with << " failed" << std::endl;
+        return nullptr;
+    }
+    uint64_t staged = 4096;
+    for (uint64_t i = 0; i < nch; i++) staged += (chunks[i].len + 4095) / 4096 * 4096;
+    cfg.batch_bytes = staged <= (256ull << 20) ? staged : 0;
+    kc_ctx* b = nullptr;
+    if (kc_create(&cfg, &b) != KC_OK) {
+        std::cerr << "kc_create (--with): " << kc_last_error(nullptr) << std::endl;
+        kc_free(chunks);
+        return nullptr;
+    }
+    int rc = KC_OK;
+    const char* what = "bloom pass";
+    if (cfg.bf_enable) {
+        for (uint64_t i = 0; i < nch && rc == KC_OK; i++)
+            rc = kc_bloom_chunk(b, img.data() + chunks[i].off, chunks[i].len, fmt, chunks[i].broken_header);
+        uint64_t nis = 0;
+        if (rc == KC_OK) rc = kc_bloom_finalize(b, &nis);
+    }
+    if (rc == KC_OK) what = "counting pass";
+    for (uint64_t i = 0; i < nch && rc == KC_OK; i++)
+        rc = kc_count_chunk(b, img.data() + chunks[i].off, chunks[i].len, fmt, chunks[i].broken_header);
+    kc_free(chunks);
+    if (rc != KC_OK) {
+        std::cerr << what << " (--with): " << kc_last_error(b) << std::endl;
+        kc_destroy(b);
+        return nullptr;
+    }
+    return b;
 }
 
 }  // namespace
@@ -931,6 +1037,58 @@ int main(int argc, char** argv) {
     if (frc != KC_OK) {
         std::cout << "Hash table is full... Cannot handle this yet\n";
         die("counting pass");
+    }
+    // --op NAME --with FILE2 (extension): FILE2 counted into a second context, the operation's result
+    // into a third -- no Bloom filter, sized from the operands' distinct k-mers -- which everything
+    // below (the output, its digest, --histo, --query, --coverage) then reads instead
+    kc_op_stats ost;
+    std::memset(&ost, 0, sizeof ost);
+    if (a.op >= 0) {
+        kc_ctx* ctx_b = count_with(a, cfg);
+        if (!ctx_b) { kc_destroy(ctx); return 1; }
+        kc_stats stb;
+        if (kc_finish(ctx_b, &stb) != KC_OK) {
+            std::cerr << "counting pass (--with): " << kc_last_error(ctx_b) << std::endl;
+            kc_destroy(ctx_b);
+            kc_destroy(ctx);
+            return 1;
+        }
+        const bool uni = a.op == KC_OP_UNION_SUM || a.op == KC_OP_UNION_MAX;
+        const uint64_t need = stt.distinct + (uni ? stb.distinct : 0);
+        kc_config rcfg = cfg;
+        rcfg.bf_enable = 0;
+        rcfg.est_unique = 0;
+        rcfg.table_slots = need + need / 8 + 4096;
+        rcfg.batch_bytes = 1 << 20;  // (nothing is staged into it)
+        kc_ctx* ctx_r = nullptr;
+        if (kc_create(&rcfg, &ctx_r) != KC_OK) {
+            std::cerr << "kc_create (--op): " << kc_last_error(nullptr) << std::endl;
+            kc_destroy(ctx_b);
+            kc_destroy(ctx);
+            return 1;
+        }
+        kc_op_desc od;
+        std::memset(&od, 0, sizeof od);
+        od.op = a.op;
+        od.a_min = (uint32_t)a.a_min;
+        od.a_max = (uint32_t)a.a_max;
+        od.b_min = (uint32_t)a.b_min;
+        od.b_max = (uint32_t)a.b_max;
+        kc_stats str;
+        if (kc_table_op(ctx_r, ctx, ctx_b, &od, &ost) != KC_OK || kc_finish(ctx_r, &str) != KC_OK) {
+            std::cerr << "table operation " << a.op_name << ": " << kc_last_error(ctx_r) << std::endl;
+            kc_destroy(ctx_r);
+            kc_destroy(ctx_b);
+            kc_destroy(ctx);
+            return 1;
+        }
+        std::cout << "Table operation " << a.op_name << " with " << filename_of(a.with) << ": " << ost.a_keys
+                  << " k-mers of the input in range, " << ost.both << " of them in the second file, " << ost.b_only
+                  << " only in the second file; result " << ost.out_keys << " k-mers (counts sum " << ost.out_sum
+                  << ") in " << str.table_slots << " slots\n";
+        kc_destroy(ctx_b);
+        kc_destroy(ctx);
+        ctx = ctx_r;  // (die reports on it from here on)
     }
     auto t1 = clk::now();
     // the reference prints its table size, next_prime3mod4(-s or 2 * new_in_second)

@@ -455,4 +455,25 @@ void drop_compact(kc_ctx* c);
 int flush_host(kc_ctx* c);
 int device_pass(kc_ctx* c, const uint8_t* img, const kc_chunk* chunks, size_t n, int fmt, int pass, hipStream_t s);
 
+// What the record / key inserts (kc_api_shard.cpp) and the table algebra (kc_api_join.cpp) share, on
+// the caller's stream (joined here unless the caller has): `size` prepares the partition buffers (or
+// the table), before the profiling bracket opens or (prof_first) after it; `work` is the launch the
+// bracket times; then the table's -- or (bloom) the filter's -- freshness flags.
+template <class Size, class Work>
+int insert_on(kc_ctx* c, StreamScope& on, bool bloom, bool prof_first, Size size, Work work) {
+    int rc = on.join();
+    if (rc) return rc;
+    if (prof_first && (rc = on.profile())) return rc;
+    if ((rc = size())) return rc;
+    if (!prof_first && (rc = on.profile())) return rc;
+    if ((rc = work())) return rc;
+    if (bloom) {
+        c->bloom_fresh = false;
+    } else {
+        own_after_write(c, false, false);
+        c->table_fresh = c->table_zero_pending = false;
+    }
+    return on.finish();
+}
+
 #pragma GCC visibility pop

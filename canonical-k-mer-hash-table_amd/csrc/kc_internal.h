@@ -439,9 +439,28 @@ hipError_t launch_seq_reduce(const uint32_t* counts, uint64_t base, const uint64
                              const uint64_t* long_ids, uint64_t n_long, int k, uint32_t solid_min, kc_seq_stat* stats,
                              hipStream_t s);
 
-// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip): Ops is WOps, CompactOps, QueryOps or SeqOps, whose
+// Table algebra (kc_join_impl.h): one sweep of table x a bucket per thread; every key of x whose
+// T(c) lies in [x_min, x_max] (x_max 0 = no upper bound) is looked up in y (its own geometry; it
+// counts as held when its T(c) lies in y's range) and r = op(cx, cy) on the raw counts (KC_OP_*,
+// cy = 0 when y does not hold it) is added into dst (dst.buckets == nullptr: nothing is inserted).
+// second != 0: the UNION operations' second launch, x = b and y = a -- only the keys y does not
+// hold yield a record, r = cx.  x and y are only read.  stats (nullptr: none): the five words of
+// kc_op_stats, added to (the first launch a_keys, both, out_keys, out_sum; the second b_only,
+// out_keys, out_sum); ctr (dst's, nullptr without dst): inserted += the counts added, overflow +=
+// the inserts that found their region full.
+template <int W>
+struct JoinOps {
+    static hipError_t join(TableView x, TableView y, TableView dst, int mode_x, int mode_y, uint32_t x_min,
+                           uint32_t x_max, uint32_t y_min, uint32_t y_max, int op, int second, DevCounters* ctr,
+                           unsigned long long* stats, hipStream_t s);
+};
+hipError_t launch_join(TableView x, TableView y, TableView dst, int mode_x, int mode_y, uint32_t x_min, uint32_t x_max,
+                       uint32_t y_min, uint32_t y_max, int op, int second, DevCounters* ctr, unsigned long long* stats,
+                       hipStream_t s);
+
+// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip): Ops is WOps, CompactOps, QueryOps, SeqOps or JoinOps, whose
 // members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

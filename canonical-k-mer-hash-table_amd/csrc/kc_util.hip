@@ -1,7 +1,7 @@
 // kc_util.hip -- small device helpers: the device XXH64 of the reference-layout Bloom
 // passes (kc_common.h xxh64_u64) over host-given inputs (test hook), the chunk checksum of
 // the partition reuse, the sharded Bloom filter's merge and filter-2 bit count, and the
-// W-dispatch of the table queries (kc_query_w.hip).
+// W-dispatch of the table queries (kc_query_w.hip) and of the table algebra (kc_join_w.hip).
 #include "kc_common.h"
 
 namespace kc {
@@ -160,6 +160,13 @@ hipError_t launch_lookup(TableView t, int k, int count_mode, int layout, const u
 }
 hipError_t launch_histo(TableView t, int count_mode, uint32_t n_bins, unsigned long long* hist, hipStream_t s) {
     KC_DISPATCH(QueryOps, t.W, histo(t, count_mode, n_bins, hist, s));
+}
+
+// W-dispatch of the table algebra (kc_join_w.hip, one translation unit per key width)
+hipError_t launch_join(TableView x, TableView y, TableView dst, int mode_x, int mode_y, uint32_t x_min, uint32_t x_max,
+                       uint32_t y_min, uint32_t y_max, int op, int second, DevCounters* ctr, unsigned long long* stats,
+                       hipStream_t s) {
+    KC_DISPATCH(JoinOps, x.W, join(x, y, dst, mode_x, mode_y, x_min, x_max, y_min, y_max, op, second, ctr, stats, s));
 }
 
 }  // namespace kc

@@ -58,7 +58,13 @@ EXPORTS = (
     "kc_output_digest", "kc_route_superkmers_device", "kc_count_packed_device", "kc_bloom_packed_device",
     "kc_lookup_device", "kc_lookup", "kc_histogram",
     "kc_text_counts_device", "kc_text_counts", "kc_seq_stats_device", "kc_seq_stats",
+    "kc_table_op_device", "kc_table_op",
 )
+# kc_table_op* operations (KC_OP_*): on the raw counts ca, cb of a key in a and in b
+OP_INTERSECT_MIN, OP_INTERSECT_SUM, OP_INTERSECT_LEFT, OP_SUBTRACT, OP_COUNTS_SUBTRACT, OP_UNION_SUM, OP_UNION_MAX = range(7)
+OP_NAMES = {"intersect-min": OP_INTERSECT_MIN, "intersect-sum": OP_INTERSECT_SUM, "intersect-left": OP_INTERSECT_LEFT,
+            "subtract": OP_SUBTRACT, "counts-subtract": OP_COUNTS_SUBTRACT, "union-sum": OP_UNION_SUM,
+            "union-max": OP_UNION_MAX}
 
 
 class KcError(RuntimeError):
@@ -96,6 +102,18 @@ class kc_compact_info(ctypes.Structure):
 
 class kc_digest(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("lines", "count_sum", "hash_sum", "hash_xor")]
+
+
+class kc_op_desc(ctypes.Structure):  # 24 bytes
+    _fields_ = [("op", ctypes.c_int32), ("a_min", ctypes.c_uint32), ("a_max", ctypes.c_uint32),
+                ("b_min", ctypes.c_uint32), ("b_max", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class kc_op_stats(ctypes.Structure):  # 40 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("a_keys", "both", "b_only", "out_keys", "out_sum")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class kc_stats(ctypes.Structure):
@@ -198,6 +216,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_text_counts": (I32, [P, P, U64, P]),
         "kc_seq_stats_device": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P, P]),
         "kc_seq_stats": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P]),
+        "kc_table_op_device": (I32, [P, P, P, ctypes.POINTER(kc_op_desc), P, P]),
+        "kc_table_op": (I32, [P, P, P, ctypes.POINTER(kc_op_desc), ctypes.POINTER(kc_op_stats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -675,6 +695,24 @@ class KmerCounter:
                                             out.ctypes.data), "kc_seq_stats")
         return out
 
+    # -- table algebra (kc_table_op*): this counter is the destination
+    def table_op_device(self, a: "KmerCounter", b: "KmerCounter", op: int, a_range=(1, 0), b_range=(1, 0),
+                        stats_ptr: int = 0, stream: int = 0):
+        """self += op(a, b) on the raw counts (OP_*), all in HBM: a key of a takes part when
+        a_range[0] <= T(c) <= a_range[1] (a max of 0: no upper bound), the same for b.  stats_ptr: 40
+        bytes of device memory for the kc_op_stats (0: none); enqueued on `stream`, no wait."""
+        d = _op_desc(op, a_range, b_range)
+        self._chk(self.lib.kc_table_op_device(self._ctx, a._ctx, b._ctx, ctypes.byref(d),
+                                              ctypes.c_void_p(stats_ptr or None), ctypes.c_void_p(stream or None)),
+                  "kc_table_op_device")
+
+    def table_op(self, a: "KmerCounter", b: "KmerCounter", op: int, a_range=(1, 0), b_range=(1, 0)) -> dict:
+        """table_op_device that waits; returns the statistics: a_keys (keys of a in its range), both
+        (of those, in b), b_only (UNION ops only), out_keys and out_sum (the records added here)."""
+        d, st = _op_desc(op, a_range, b_range), kc_op_stats()
+        self._chk(self.lib.kc_table_op(self._ctx, a._ctx, b._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_table_op")
+        return st.as_dict()
+
     def compact_read(self, info: dict):
         """(slot words, secondary-array words) as uint64 arrays."""
         W = self.lib.kc_key_words(self._ctx)
@@ -698,6 +736,23 @@ class KmerCounter:
         d = kc_digest()
         self._chk(self.lib.kc_output_digest(self._ctx, ctypes.byref(d)), "kc_output_digest")
         return digest_dict(d.lines, d.count_sum, d.hash_sum, d.hash_xor)
+
+
+def _op_desc(op: int, a_range, b_range) -> kc_op_desc:
+    return kc_op_desc(int(op), int(a_range[0]), int(a_range[1]), int(b_range[0]), int(b_range[1]), 0)
+
+
+def table_compare(a: KmerCounter, b: KmerCounter, a_range=(1, 0), b_range=(1, 0)) -> dict:
+    """Compare two counted tables in HBM (kc_table_op without a destination, OP_UNION_SUM): the
+    statistics of KmerCounter.table_op plus jaccard = both / (a_keys + b_only) and containment (of a
+    in b) = both / a_keys, 0.0 where the denominator is 0.  Nothing is inserted anywhere."""
+    d, st = _op_desc(OP_UNION_SUM, a_range, b_range), kc_op_stats()
+    a._chk(a.lib.kc_table_op(None, a._ctx, b._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_table_op")
+    r = st.as_dict()
+    union = r["a_keys"] + r["b_only"]
+    r["jaccard"] = r["both"] / union if union else 0.0
+    r["containment"] = r["both"] / r["a_keys"] if r["a_keys"] else 0.0
+    return r
 
 
 def digest_dict(lines: int, count_sum: int, hash_sum: int, hash_xor: int) -> dict:

@@ -394,6 +394,67 @@ int kc_seq_stats_device(kc_ctx* ctx, const uint8_t* dev_text, uint64_t n_bytes, 
 int kc_seq_stats(kc_ctx* ctx, const uint8_t* text, uint64_t n_bytes, const uint64_t* offsets, uint64_t n_seqs,
                  uint32_t solid_min, kc_seq_stat* stats);
 
+/* Table algebra: relate two counted tables in HBM.  The reference has no counterpart -- it counts
+ * one input into one table, and its users join output files (k-mers of the child absent from the
+ * mother, k-mers two runs share, a sample minus an adapter set, Jaccard similarity, the union of
+ * several runs).  One fused kernel sweeps a's table, looks every key up in b's and adds the
+ * operation's result into dst's table: no key or record goes through HBM between the three, and
+ * nothing crosses to the host.  The UNION operations run it a second time over b for the keys a
+ * lacks.  The result is itself a counted table: kc_write, kc_output_digest, kc_histogram,
+ * kc_lookup*, kc_seq_stats*, kc_compact and a further kc_table_op work on dst unchanged.
+ *   kc_table_op_device  dst += op(a, b).
+ *     Counts are the RAW counts of the slots, the counts kc_route_table_device and
+ *     kc_insert_counts_device move; T(c) is not applied to them, dst applies its own -m when it is
+ *     read.  So in -m 1/2 min, max and sum saturate AFTER the operation: KC_OP_COUNTS_SUBTRACT of
+ *     k-mers counted 20000 and 17000 times reads back 3000, KC_OP_INTERSECT_SUM of them 16383.
+ *     A key of a is "in a" when a_min <= T(c) <= a_max, T(c) being the count kc_lookup reports for
+ *     it in a's own mode (c mod 65536 for -m 0, min(c, 16383) otherwise); the same for b with
+ *     b_min / b_max.  A min of 0 means 1, a max of 0 no upper bound.  A key outside its table's
+ *     range counts as absent from that table.  The minimum abundance -a is applied nowhere.
+ *     The results are ADDED into dst's table, as kc_insert_counts_device adds records: a dst
+ *     fresh from kc_create, kc_reset or kc_clear_table holds exactly the result, repeated calls
+ *     accumulate (the union of many tables, one call each).  dst's counters change as they do for
+ *     kc_insert_counts_device (kc_stats.inserted += the counts added); a result that does not
+ *     fit dst's table makes kc_finish on dst return KC_ERR_TABLE_FULL.  a's and b's tables and
+ *     kc_stats do not change; dst may have any table size, and so may a and b (a table's keys do
+ *     not depend on its geometry), any mode, and a or b may be Bloom-gated.
+ *     dst == NULL inserts nothing and fills only the statistics; with a UNION operation that is
+ *     the comparison of two samples: Jaccard = both / (a_keys + b_only), containment of a in b =
+ *     both / a_keys.  dev_stats (device memory, may be NULL) is zeroed and filled by the call.
+ *     a == b is allowed.  KC_ERR_ARG: dst equal to a or b, contexts of different k or device, an
+ *     unknown op, reserved != 0, a min above a non-zero max, a NULL a, b or op.  KC_ERR_STATE: one
+ *     of the three without a table (a Bloom context before kc_bloom_finalize) or with a job a
+ *     failed pass left incomplete.  An a or b emptied by kc_reset or kc_clear_table holds no key.
+ *     The message of a failed call is on dst (kc_last_error), on a when dst is NULL.
+ *     Follows the *_device rule for ALL THREE contexts: the staged host chunks of each are
+ *     flushed first, the work runs on hip_stream after what is queued there and after each
+ *     context's own stream, and each context's later work follows it; no host wait (unless dst
+ *     holds a compact representation, which is dropped: it is a snapshot of the table before).
+ *   kc_table_op         the same with the statistics in host memory (may be NULL); waits. */
+#define KC_OP_INTERSECT_MIN   0  /* keys in both;            min(ca, cb) */
+#define KC_OP_INTERSECT_SUM   1  /* keys in both;            ca + cb     */
+#define KC_OP_INTERSECT_LEFT  2  /* keys in both;            ca          */
+#define KC_OP_SUBTRACT        3  /* keys of a not in b;      ca          */
+#define KC_OP_COUNTS_SUBTRACT 4  /* keys of a; ca - cb where positive (cb = 0 if absent), else dropped */
+#define KC_OP_UNION_SUM       5  /* keys in either;          ca + cb     */
+#define KC_OP_UNION_MAX       6  /* keys in either;          max(ca, cb) */
+typedef struct {            /* 24 bytes */
+    int32_t  op;
+    uint32_t a_min, a_max;  /* a key of a is "in a" when a_min <= T(c) <= a_max; a_min 0 means 1, a_max 0 = no upper bound */
+    uint32_t b_min, b_max;  /* the same for b */
+    uint32_t reserved;      /* 0 */
+} kc_op_desc;
+typedef struct {            /* 40 bytes */
+    uint64_t a_keys;   /* keys in a (inside its range) */
+    uint64_t both;     /* of those, in b (inside its range) */
+    uint64_t b_only;   /* keys in b and not in a -- UNION ops only (the only ones that sweep b), else 0 */
+    uint64_t out_keys; /* records the operation yields (added to dst when dst != NULL) */
+    uint64_t out_sum;  /* sum of their counts */
+} kc_op_stats;
+int kc_table_op_device(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, kc_op_stats* dev_stats,
+                       void* hip_stream);
+int kc_table_op(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, kc_op_stats* stats);
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
