@@ -65,6 +65,11 @@ struct Args {
     // counts of another file's sequences (kc_seq_stats); N (a k-mer is solid from this count on)
     // defaults to the -a value
     std::string coverage, coverage_out;
+    // --correct FILE --correct-out FILE [--correct-min N]: the file's sequences with their isolated
+    // base errors corrected from the table (kc_correct), written back in the file's format
+    std::string correct, correct_out;
+    unsigned long long correct_min = 0;
+    bool correct_min_set = false;
     unsigned long long coverage_min = 0;
     bool coverage_min_set = false;
     // --op NAME --with FILE2 [--a-min/--a-max/--b-min/--b-max N]: FILE2 is counted like INPUT into a
@@ -102,6 +107,11 @@ void usage(const char* prog) {
                  "  --coverage-out FILE         per record, tab-separated: name length windows present solid min\n"
                  "                              median max sum (of its k-mers' counts); needed with --coverage\n"
                  "  --coverage-min UINT         a k-mer is solid from this count on (def. the -a value)\n"
+                 "  --correct FILE              sequences (FASTA, FASTQ or one per line) whose isolated base errors\n"
+                 "                              to correct: a base all of whose k-mers are weak and that exactly\n"
+                 "                              one other base makes solid\n"
+                 "  --correct-out FILE          the corrected records, in the format of FILE; needed with --correct\n"
+                 "  --correct-min UINT          a k-mer is solid from this count on (def. the -a value)\n"
                  "  --op NAME                   output a table operation on INPUT (a) and the --with file (b): intersect-min,\n"
                  "                              intersect-sum, intersect-left, subtract, counts-subtract, union-sum, union-max\n"
                  "  --with FILE                 the second input, counted with the same options; needed with --op\n"
@@ -290,6 +300,15 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 a->coverage_min = u;
                 a->coverage_min_set = true;
+            } else if (o == "--correct") {
+                a->correct = v;
+            } else if (o == "--correct-out") {
+                a->correct_out = v;
+            } else if (o == "--correct-min") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                a->correct_min = u;
+                a->correct_min_set = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -336,6 +355,10 @@ int parse(int argc, char** argv, Args* a) {
         return cli_error(kRequires, "--coverage-out requires --coverage");
     if (a->coverage_min_set && a->coverage.empty()) return cli_error(kRequires, "--coverage-min requires --coverage");
     if (!a->coverage_min_set) a->coverage_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if (!a->correct.empty() && a->correct_out.empty()) return cli_error(kRequires, "--correct requires --correct-out");
+    if (a->correct.empty() && !a->correct_out.empty()) return cli_error(kRequires, "--correct-out requires --correct");
+    if (a->correct_min_set && a->correct.empty()) return cli_error(kRequires, "--correct-min requires --correct");
+    if (!a->correct_min_set) a->correct_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -558,22 +581,27 @@ int read_queries(const std::string& path, int k, std::vector<std::string>* lines
 // spans two records -- with offsets[i] the start of record i (kc_seq_stats).  A record's name is
 // its header's first whitespace-delimited token without the '>' or '@'; in a plain file its
 // 1-based line number.  Returns -1 on success, else the exit code.
+// --correct FILE reads its records the same way (opt names the option in the messages) and writes
+// them back in the file's format, so the whole header lines and a FASTQ record's '+' and quality
+// lines are kept too (without their CR).
 struct Coverage {
     std::string text;
     std::vector<uint64_t> offsets;
     std::vector<std::string> names;
     std::vector<uint64_t> lengths;
+    int fmt = KC_FMT_PLAIN;
+    std::vector<std::string> headers, plus, quals;
 };
-int read_coverage(const std::string& path, Coverage* cv) {
+int read_coverage(const std::string& path, Coverage* cv, const std::string& opt = "--coverage") {
     FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return cli_error(kValidation, "--coverage: File does not exist: " + path);
+    if (!f) return cli_error(kValidation, opt + ": File does not exist: " + path);
     std::string data;
     char buf[1 << 16];
     size_t got;
     while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) data.append(buf, got);
     std::fclose(f);
     if (data.size() >= 2 && (unsigned char)data[0] == 0x1f && (unsigned char)data[1] == 0x8b)
-        return cli_error(kValidation, "--coverage: gzip input is not supported: " + path);
+        return cli_error(kValidation, opt + ": gzip input is not supported: " + path);
     const std::string ext = ext_of(path);
     const unsigned char sym = data.empty() ? 0 : (unsigned char)data[0];
     int fmt;
@@ -581,7 +609,8 @@ int read_coverage(const std::string& path, Coverage* cv) {
     if (ext == ".fasta" || ext == ".fa") { fmt = KC_FMT_FASTA; ill = sym != '>'; }
     else if (ext == ".fastq" || ext == ".fq") { fmt = KC_FMT_FASTQ; ill = sym != '@'; }
     else { fmt = KC_FMT_PLAIN; ill = !(sym && std::strchr("actgACGT", sym)); }
-    if (ill) return cli_error(kValidation, "--coverage: Input file " + path + " is ill-formed");
+    if (ill) return cli_error(kValidation, opt + ": Input file " + path + " is ill-formed");
+    cv->fmt = fmt;
     auto name_of = [](const std::string& header) {
         size_t e = 1;
         while (e < header.size() && !std::isspace((unsigned char)header[e])) e++;
@@ -611,6 +640,7 @@ int read_coverage(const std::string& path, Coverage* cv) {
             if (!line.empty() && line[0] == '>') {
                 if (in_record) close_record();
                 open_record(name_of(line));
+                cv->headers.push_back(line);
                 in_record = true;
             } else if (in_record) {
                 add_sequence(line);
@@ -619,12 +649,17 @@ int read_coverage(const std::string& path, Coverage* cv) {
             if (phase == 0 && line.empty()) continue;
             if (phase == 0) {
                 if (line[0] != '@')
-                    return cli_error(kValidation, "--coverage: line " + std::to_string(lineno) + " of " + path +
+                    return cli_error(kValidation, opt + ": line " + std::to_string(lineno) + " of " + path +
                                                       " is not a FASTQ header");
                 open_record(name_of(line));
+                cv->headers.push_back(line);
             } else if (phase == 1) {
                 add_sequence(line);
                 close_record();
+            } else if (phase == 2) {
+                cv->plus.push_back(line);
+            } else {
+                cv->quals.push_back(line);
             }
             phase = (phase + 1) & 3;
         } else if (!line.empty()) {
@@ -636,6 +671,10 @@ int read_coverage(const std::string& path, Coverage* cv) {
     if (fmt == KC_FMT_FASTA && in_record) close_record();
     if (fmt == KC_FMT_FASTQ && phase == 1) close_record();  // (a header with nothing after it)
     cv->offsets.push_back(cv->text.size());
+    if (fmt == KC_FMT_FASTQ) {  // (a last record cut short)
+        cv->plus.resize(cv->names.size(), "+");
+        cv->quals.resize(cv->names.size());
+    }
     return -1;
 }
 
@@ -725,6 +764,11 @@ int main(int argc, char** argv) {
     Coverage cov;  // --coverage: read and checked before anything else runs, too
     if (!a.coverage.empty()) {
         const int crc = read_coverage(a.coverage, &cov);
+        if (crc >= 0) return crc;
+    }
+    Coverage fix;  // --correct: the same
+    if (!a.correct.empty()) {
+        const int crc = read_coverage(a.correct, &fix, "--correct");
         if (crc >= 0) return crc;
     }
 
@@ -1040,7 +1084,7 @@ int main(int argc, char** argv) {
     }
     // --op NAME --with FILE2 (extension): FILE2 counted into a second context, the operation's result
     // into a third -- no Bloom filter, sized from the operands' distinct k-mers -- which everything
-    // below (the output, its digest, --histo, --query, --coverage) then reads instead
+    // below (the output, its digest, --histo, --query, --coverage, --correct) then reads instead
     kc_op_stats ost;
     std::memset(&ost, 0, sizeof ost);
     if (a.op >= 0) {
@@ -1141,6 +1185,35 @@ int main(int argc, char** argv) {
                          cst[i].median, cst[i].max, (unsigned long long)cst[i].sum);
         if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.coverage_out << std::endl; kc_destroy(ctx); return 1; }
     }
+    if (!a.correct.empty()) {  // extension: the records with their isolated base errors corrected
+        const size_t nrec = fix.names.size();
+        std::vector<kc_correct_stat> fst(nrec);
+        std::string fixed(fix.text.size(), '\0');
+        if (kc_correct(ctx, (const uint8_t*)fix.text.data(), fix.text.size(), fix.offsets.data(), nrec,
+                       (uint32_t)a.correct_min, (uint8_t*)&fixed[0], fst.data()) != KC_OK)
+            die("read correction");
+        FILE* f = std::fopen(a.correct_out.c_str(), "w");
+        if (!f) { std::cerr << "cannot write " << a.correct_out << std::endl; kc_destroy(ctx); return 1; }
+        unsigned long long bases = 0, recs = 0, cands = 0, ambig = 0, dropped = 0;
+        for (size_t i = 0; i < nrec; i++) {
+            const std::string seq = fixed.substr(fix.offsets[i], fix.lengths[i]);
+            if (fix.fmt == KC_FMT_FASTA)
+                std::fprintf(f, "%s\n%s\n", fix.headers[i].c_str(), seq.c_str());
+            else if (fix.fmt == KC_FMT_FASTQ)
+                std::fprintf(f, "%s\n%s\n%s\n%s\n", fix.headers[i].c_str(), seq.c_str(), fix.plus[i].c_str(),
+                             fix.quals[i].c_str());
+            else
+                std::fprintf(f, "%s\n", seq.c_str());
+            bases += fst[i].corrected;
+            recs += fst[i].corrected != 0;
+            cands += fst[i].candidates;
+            ambig += fst[i].ambiguous;
+            dropped += fst[i].dropped;
+        }
+        if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.correct_out << std::endl; kc_destroy(ctx); return 1; }
+        std::cout << "Corrected " << bases << " bases in " << recs << " of " << nrec << " records (" << cands
+                  << " candidates, " << ambig << " ambiguous, " << dropped << " dropped)\n";
+    }
     auto t3 = clk::now();
     std::cout << "Time used to build hash table: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() + (a.use_bf ? 0 : prep_us)
@@ -1151,7 +1224,7 @@ int main(int argc, char** argv) {
                   << " stays the reference capacity)\n";
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
-    if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty())
+    if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty())
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
                   << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")

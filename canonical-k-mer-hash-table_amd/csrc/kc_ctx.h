@@ -240,6 +240,9 @@ struct kc_ctx {
     DevBuf<uint64_t> d_seq_off;
     PinnedBuf<uint64_t> h_seq_off;
     hipEvent_t seq_ev = nullptr;
+    // read correction (kc_api_correct.cpp): a verdict byte per position of a pass, beside the
+    // sequence queries' stream, counts and offsets
+    DevBuf<uint8_t> d_cor_vd;
 
     uint64_t n_chunks = 0, n_bytes = 0;
 

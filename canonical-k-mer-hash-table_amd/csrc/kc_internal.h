@@ -439,6 +439,31 @@ hipError_t launch_seq_reduce(const uint32_t* counts, uint64_t base, const uint64
                              const uint64_t* long_ids, uint64_t n_long, int k, uint32_t solid_min, kc_seq_stat* stats,
                              hipStream_t s);
 
+// Read correction (kc_correct.hip, kc_correct_impl.h; the rule: include/kc_api.h kc_correct_device).
+// One pass of n_pos text bytes from byte `base` on, holding the sequences i0 .. i1 - 1 of the device
+// offsets off, after launch_seq_pack / launch_seq_counts of the same pass: mark writes verdict[p] =
+// CV_CAND or 0 for every position, try (attempt) rewrites the candidates' verdicts (CV_AMBIG, or
+// CV_ACC with the working base code in the low two bits), apply writes out[p] for every position
+// (text, out: the pass's first byte; out == text allowed) and adds the sequences' counters into
+// stats (indexed by sequence; nullptr: none; zeroed by the caller).  smin >= 1.
+constexpr int CORRECT_TILE = 1024;   // positions per workgroup of k_correct_mark
+constexpr int CORRECT_HALO = 512;    // the positions before them it also reads (>= MAX_K - 1)
+constexpr uint8_t CV_CAND = 0x80, CV_AMBIG = 0x40, CV_ACC = 0x20;
+template <int W>
+struct CorrectOps {
+    static hipError_t attempt(TableView t, PackedView sv, const uint32_t* counts, uint64_t n_pos, uint64_t base,
+                              const uint64_t* off, uint64_t i0, uint64_t i1, int k, int count_mode, uint32_t smin,
+                              uint8_t* verdict, hipStream_t s);
+};
+hipError_t launch_correct_mark(const uint32_t* counts, uint64_t n_pos, uint64_t base, const uint64_t* off, uint64_t i0,
+                               uint64_t i1, int k, uint32_t smin, uint8_t* verdict, hipStream_t s);
+hipError_t launch_correct_try(TableView t, PackedView sv, const uint32_t* counts, uint64_t n_pos, uint64_t base,
+                              const uint64_t* off, uint64_t i0, uint64_t i1, int k, int count_mode, uint32_t smin,
+                              uint8_t* verdict, hipStream_t s);
+hipError_t launch_correct_apply(const uint8_t* text, uint8_t* out, const uint8_t* verdict, uint64_t n_pos,
+                                uint64_t base, const uint64_t* off, uint64_t i0, uint64_t i1, int k,
+                                kc_correct_stat* stats, hipStream_t s);
+
 // Table algebra (kc_join_impl.h): one sweep of table x a bucket per thread; every key of x whose
 // T(c) lies in [x_min, x_max] (x_max 0 = no upper bound) is looked up in y (its own geometry; it
 // counts as held when its T(c) lies in y's range) and r = op(cx, cy) on the raw counts (KC_OP_*,
@@ -458,9 +483,9 @@ hipError_t launch_join(TableView x, TableView y, TableView dst, int mode_x, int 
                        uint32_t y_min, uint32_t y_max, int op, int second, DevCounters* ctr, unsigned long long* stats,
                        hipStream_t s);
 
-// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip): Ops is WOps, CompactOps, QueryOps, SeqOps or JoinOps, whose
-// members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
+// JoinOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

@@ -43,6 +43,8 @@ NO_KMER = 0xFFFFFFFF  # kc_text_counts*: no k-mer starts at this position (KC_NO
 # kc_seq_stat (include/kc_api.h), 32 bytes
 SEQ_STAT_DTYPE = np.dtype([("windows", "<u4"), ("present", "<u4"), ("solid", "<u4"), ("min", "<u4"),
                            ("median", "<u4"), ("max", "<u4"), ("sum", "<u8")])
+# kc_correct_stat (include/kc_api.h), 16 bytes
+CORRECT_STAT_DTYPE = np.dtype([("candidates", "<u4"), ("corrected", "<u4"), ("ambiguous", "<u4"), ("dropped", "<u4")])
 
 # Public C-ABI symbols (include/kc_api.h); tests check every one is exported.
 EXPORTS = (
@@ -59,6 +61,7 @@ EXPORTS = (
     "kc_lookup_device", "kc_lookup", "kc_histogram",
     "kc_text_counts_device", "kc_text_counts", "kc_seq_stats_device", "kc_seq_stats",
     "kc_table_op_device", "kc_table_op",
+    "kc_correct_device", "kc_correct",
 )
 # kc_table_op* operations (KC_OP_*): on the raw counts ca, cb of a key in a and in b
 OP_INTERSECT_MIN, OP_INTERSECT_SUM, OP_INTERSECT_LEFT, OP_SUBTRACT, OP_COUNTS_SUBTRACT, OP_UNION_SUM, OP_UNION_MAX = range(7)
@@ -114,6 +117,10 @@ class kc_op_stats(ctypes.Structure):  # 40 bytes
 
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_correct_stat(ctypes.Structure):  # 16 bytes
+    _fields_ = [(n, ctypes.c_uint32) for n in ("candidates", "corrected", "ambiguous", "dropped")]
 
 
 class kc_stats(ctypes.Structure):
@@ -216,6 +223,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_text_counts": (I32, [P, P, U64, P]),
         "kc_seq_stats_device": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P, P]),
         "kc_seq_stats": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P]),
+        "kc_correct_device": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P, P, P]),
+        "kc_correct": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P, P]),
         "kc_table_op_device": (I32, [P, P, P, ctypes.POINTER(kc_op_desc), P, P]),
         "kc_table_op": (I32, [P, P, P, ctypes.POINTER(kc_op_desc), ctypes.POINTER(kc_op_stats)]),
     }
@@ -694,6 +703,33 @@ class KmerCounter:
             self._chk(self.lib.kc_seq_stats(self._ctx, text, len(text), off.ctypes.data, len(out), solid_min,
                                             out.ctypes.data), "kc_seq_stats")
         return out
+
+    # -- read correction (kc_correct*)
+    def correct_device(self, text_ptr: int, n_bytes: int, offsets, out_ptr: int, solid_min: int = 1,
+                       stats_ptr: int = 0, stream: int = 0):
+        """Corrects isolated base errors of a text in device memory from the table (the rule:
+        include/kc_api.h): sequence i is the bytes [offsets[i], offsets[i + 1]) (host offsets); all
+        n_bytes go to out_ptr (out_ptr == text_ptr: in place); CORRECT_STAT_DTYPE records into device
+        memory at stats_ptr (0: none); enqueued on `stream`, no wait."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_seqs = max(len(off) - 1, 0)
+        self._chk(self.lib.kc_correct_device(self._ctx, ctypes.c_void_p(text_ptr or None), n_bytes, off.ctypes.data,
+                                             n_seqs, solid_min, ctypes.c_void_p(out_ptr or None),
+                                             ctypes.c_void_p(stats_ptr or None), ctypes.c_void_p(stream or None)),
+                  "kc_correct_device")
+
+    def correct(self, seqs: Sequence, solid_min: int = 1) -> Tuple[List[bytes], np.ndarray]:
+        """The sequences (str or bytes) with their isolated base errors corrected -- a position all
+        of whose k-mers are weaker than solid_min and that exactly one other base makes solid -- and a
+        CORRECT_STAT_DTYPE array with candidates, corrected, ambiguous and dropped per sequence."""
+        text, off = pack_sequences(seqs)  # (a sequence's newline is a break: no window holds it)
+        stats = np.zeros(len(off) - 1, dtype=CORRECT_STAT_DTYPE)
+        out = ctypes.create_string_buffer(max(len(text), 1))
+        if len(stats):
+            self._chk(self.lib.kc_correct(self._ctx, text, len(text), off.ctypes.data, len(stats), solid_min, out,
+                                          stats.ctypes.data), "kc_correct")
+        fixed = out.raw[:len(text)]
+        return [fixed[int(off[i]):int(off[i + 1]) - 1] for i in range(len(stats))], stats
 
     # -- table algebra (kc_table_op*): this counter is the destination
     def table_op_device(self, a: "KmerCounter", b: "KmerCounter", op: int, a_range=(1, 0), b_range=(1, 0),

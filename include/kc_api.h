@@ -394,6 +394,50 @@ int kc_seq_stats_device(kc_ctx* ctx, const uint8_t* dev_text, uint64_t n_bytes, 
 int kc_seq_stats(kc_ctx* ctx, const uint8_t* text, uint64_t n_bytes, const uint64_t* offsets, uint64_t n_seqs,
                  uint32_t solid_min, kc_seq_stat* stats);
 
+/* Read correction: repair isolated base errors of a text from the counted table (spectrum-based
+ * correction), in one device pass -- no count and no substituted k-mer crosses to the host.  The
+ * text, the offsets and solid_min are those of kc_seq_stats*; s = max(solid_min, 1); T is
+ * kc_lookup's count (-a is not applied).  For sequence i = bytes [a, b):
+ *   windows      w with a <= w, w + k <= b and text[w .. w + k) all bases (never across two
+ *                sequences, even when they are adjacent with no break byte);
+ *   C(p)         the windows that hold position p: w <= p < w + k;
+ *   candidate(p) text[p] is a base, C(p) is not empty and every window of C(p) has T < s;
+ *   works(p, y)  y one of the three other bases: every window of C(p), with byte p replaced by y,
+ *                has T >= s;
+ *   accepted(p)  candidate(p) and exactly one y works;  ambiguous(p): two or three work;
+ *   dropped(p)   accepted(p) and another accepted q of the same sequence has |p - q| < k (all
+ *                such positions are dropped: no window of the output holds two changes).
+ * out[p] is the working y in the letter case of text[p] when p is accepted and not dropped; every
+ * other byte of the n_bytes is copied unchanged (breaks and the bytes outside [offsets[0],
+ * offsets[n_seqs]) too).  Everything is evaluated on the ORIGINAL text and the unchanged table, so
+ * the result does not depend on any order.  It follows that every window of the output that holds
+ * a changed byte has T >= s, and every other window is the input's.
+ *   kc_correct_device  dev_out receives all n_bytes; dev_out == dev_text (in place) is allowed,
+ *                     any other overlap is KC_ERR_ARG.  dev_stats (device memory, n_seqs entries,
+ *                     may be NULL) receives the kc_correct_stat below.  The text runs in passes cut
+ *                     at sequence boundaries of at most the context's staging batch
+ *                     (kc_config.batch_bytes) each, a longer single sequence being a pass of its own
+ *                     length.  Scratch of the context per text byte of a pass: 3/8 byte of packed
+ *                     stream, 4 bytes of per-position counts and 1 verdict byte (5.4 bytes; no
+ *                     candidate list is kept: the kernels find the candidates in the verdict bytes).
+ *   kc_correct        the same for host arrays (out == text allowed); waits for the answer.
+ * The *_device form follows the *_device rule exactly as kc_seq_stats_device does (no host wait
+ * beyond an earlier call's offsets copy); the argument and state errors are those of
+ * kc_seq_stats*, and a NULL text or out with n_bytes > 0 is KC_ERR_ARG.  Any table answers; an
+ * emptied one gives out == text with every base position that has covering windows a candidate.
+ * n_bytes = 0 and n_seqs = 0 are KC_OK; no counter of kc_stats changes, the table is only read. */
+typedef struct {            /* 16 bytes */
+    uint32_t candidates;    /* candidate positions */
+    uint32_t corrected;     /* accepted and not dropped: the bytes of the sequence that changed */
+    uint32_t ambiguous;     /* candidates with two or three working bases */
+    uint32_t dropped;       /* accepted positions closer than k to another accepted one */
+} kc_correct_stat;          /* a sequence without windows: every field 0 */
+int kc_correct_device(kc_ctx* ctx, const uint8_t* dev_text, uint64_t n_bytes, const uint64_t* offsets,
+                      uint64_t n_seqs, uint32_t solid_min, uint8_t* dev_out, kc_correct_stat* dev_stats,
+                      void* hip_stream);
+int kc_correct(kc_ctx* ctx, const uint8_t* text, uint64_t n_bytes, const uint64_t* offsets, uint64_t n_seqs,
+               uint32_t solid_min, uint8_t* out, kc_correct_stat* stats);
+
 /* Table algebra: relate two counted tables in HBM.  The reference has no counterpart -- it counts
  * one input into one table, and its users join output files (k-mers of the child absent from the
  * mother, k-mers two runs share, a sample minus an adapter set, Jaccard similarity, the union of
