@@ -78,6 +78,13 @@ struct Args {
     int op = -1;
     unsigned long long a_min = 0, a_max = 0, b_min = 0, b_max = 0;
     bool range_set = false;
+    // --graph FILE [--graph-min N] [--graph-max N] [--graph-stats FILE]: the de Bruijn graph of the
+    // counted k-mers (kc_graph): a line per node with its edges and unitig links, and the graph's
+    // statistics; N (a k-mer is a node when its count is in the range) defaults to the -a value and
+    // to no upper bound
+    std::string graph, graph_stats;
+    unsigned long long graph_min = 0, graph_max = 0;
+    bool graph_min_set = false, graph_max_set = false;
 };
 
 const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
@@ -116,7 +123,14 @@ void usage(const char* prog) {
                  "                              intersect-sum, intersect-left, subtract, counts-subtract, union-sum, union-max\n"
                  "  --with FILE                 the second input, counted with the same options; needed with --op\n"
                  "  --a-min,--a-max,--b-min,--b-max UINT\n"
-                 "                              a k-mer takes part when its count is in its file's range (def. 1 and up)\n\n"
+                 "                              a k-mer takes part when its count is in its file's range (def. 1 and up)\n"
+                 "  --graph FILE                write the de Bruijn graph of the counted k-mers, a line per node:\n"
+                 "                              \"<k-mer> <count> <R> <L> <links>\" -- R, L: the bases that follow and\n"
+                 "                              precede it (A..T: A and T do), links: its unitig links (--, -R, L-, LR)\n"
+                 "  --graph-min,--graph-max UINT\n"
+                 "                              a k-mer is a node when its count is in this range (def. the -a value and\n"
+                 "                              up); needs --graph\n"
+                 "  --graph-stats FILE          write the graph's statistics as \"<name> <value>\" lines\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -309,6 +323,15 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 a->correct_min = u;
                 a->correct_min_set = true;
+            } else if (o == "--graph") {
+                a->graph = v;
+            } else if (o == "--graph-stats") {
+                a->graph_stats = v;
+            } else if (o == "--graph-min" || o == "--graph-max") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                (o == "--graph-min" ? a->graph_min : a->graph_max) = u;
+                (o == "--graph-min" ? a->graph_min_set : a->graph_max_set) = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -359,6 +382,11 @@ int parse(int argc, char** argv, Args* a) {
     if (a->correct.empty() && !a->correct_out.empty()) return cli_error(kRequires, "--correct-out requires --correct");
     if (a->correct_min_set && a->correct.empty()) return cli_error(kRequires, "--correct-min requires --correct");
     if (!a->correct_min_set) a->correct_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if ((a->graph_min_set || a->graph_max_set) && a->graph.empty())
+        return cli_error(kRequires, "--graph-min/--graph-max require --graph");
+    if (!a->graph_min_set) a->graph_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if (a->graph_max && a->graph_min > a->graph_max)
+        return cli_error(kValidation, "--graph-min: a minimum above its maximum");
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -1214,6 +1242,53 @@ int main(int argc, char** argv) {
         std::cout << "Corrected " << bases << " bases in " << recs << " of " << nrec << " records (" << cands
                   << " candidates, " << ambig << " ambiguous, " << dropped << " dropped)\n";
     }
+    if (!a.graph.empty() || !a.graph_stats.empty()) {  // extension: the de Bruijn graph of the counted k-mers
+        uint64_t* grec = nullptr;
+        uint64_t gn = 0;
+        kc_graph_stats gst;
+        const bool lines = !a.graph.empty();
+        if (kc_graph(ctx, (uint32_t)a.graph_min, (uint32_t)a.graph_max, lines ? &grec : nullptr, lines ? &gn : nullptr,
+                     &gst) != KC_OK)
+            die("de Bruijn graph");
+        if (lines) {
+            FILE* f = std::fopen(a.graph.c_str(), "w");
+            if (!f) { std::cerr << "cannot write " << a.graph << std::endl; kc_free(grec); kc_destroy(ctx); return 1; }
+            const int W = kc_key_words(ctx), k = (int)a.k;
+            std::string line((size_t)k, 'A');
+            for (uint64_t i = 0; i < gn; i++) {
+                const uint64_t* r = grec + i * (W + 1);
+                for (int j = 0; j < k; j++) {  // character j: bits 2(k-1-j).. of the 64 W-bit key
+                    const int bit = 2 * (k - 1 - j);
+                    line[j] = "ACGT"[(r[W - 1 - bit / 64] >> (bit % 64)) & 3];
+                }
+                const uint32_t fl = (uint32_t)(r[W] >> 32);
+                char e[10];
+                for (int y = 0; y < 4; y++) {
+                    e[y] = fl & KC_GRAPH_EDGE_R(y) ? "ACGT"[y] : '.';
+                    e[5 + y] = fl & KC_GRAPH_EDGE_L(y) ? "ACGT"[y] : '.';
+                }
+                e[4] = ' ';
+                e[9] = '\0';
+                std::fprintf(f, "%s %u %s %c%c\n", line.c_str(), (uint32_t)r[W], e, fl & KC_GRAPH_LINK_L ? 'L' : '-',
+                             fl & KC_GRAPH_LINK_R ? 'R' : '-');
+            }
+            kc_free(grec);
+            if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.graph << std::endl; kc_destroy(ctx); return 1; }
+        }
+        const unsigned long long open_unitigs = gst.nodes - gst.link_ends / 2;
+        if (!a.graph_stats.empty()) {
+            FILE* f = std::fopen(a.graph_stats.c_str(), "w");
+            if (!f) { std::cerr << "cannot write " << a.graph_stats << std::endl; kc_destroy(ctx); return 1; }
+            std::fprintf(f, "nodes %llu\nedge_ends %llu\nlink_ends %llu\nisolated %llu\npalindromes %llu\n",
+                         (unsigned long long)gst.nodes, (unsigned long long)gst.edge_ends, (unsigned long long)gst.link_ends,
+                         (unsigned long long)gst.isolated, (unsigned long long)gst.palindromes);
+            for (int d = 0; d < 5; d++) std::fprintf(f, "side_degree_%d %llu\n", d, (unsigned long long)gst.side_degree[d]);
+            std::fprintf(f, "open_unitigs %llu\n", open_unitigs);
+            if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.graph_stats << std::endl; kc_destroy(ctx); return 1; }
+        }
+        std::cout << "De Bruijn graph: " << gst.nodes << " nodes, " << gst.edge_ends << " edge ends, " << gst.link_ends
+                  << " link ends, " << open_unitigs << " open unitigs\n";
+    }
     auto t3 = clk::now();
     std::cout << "Time used to build hash table: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() + (a.use_bf ? 0 : prep_us)
@@ -1224,7 +1299,8 @@ int main(int argc, char** argv) {
                   << " stays the reference capacity)\n";
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
-    if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty())
+    if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty() || !a.graph.empty() ||
+        !a.graph_stats.empty())
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
                   << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")

@@ -243,6 +243,10 @@ struct kc_ctx {
     // read correction (kc_api_correct.cpp): a verdict byte per position of a pass, beside the
     // sequence queries' stream, counts and offsets
     DevBuf<uint8_t> d_cor_vd;
+    // the de Bruijn graph (kc_api_graph.cpp): an edge byte per table slot, and the statistics words
+    // followed by the record cursor (GRAPH_STAT_WORDS)
+    DevBuf<uint8_t> d_graph_edges;
+    DevBuf<unsigned long long> d_graph_stat;
 
     uint64_t n_chunks = 0, n_bytes = 0;
 

@@ -483,9 +483,30 @@ hipError_t launch_join(TableView x, TableView y, TableView dst, int mode_x, int 
                        uint32_t y_min, uint32_t y_max, int op, int second, DevCounters* ctr, unsigned long long* stats,
                        hipStream_t s);
 
+// The de Bruijn graph of the counted table (kc_graph_impl.h; the definitions: include/kc_api.h
+// kc_graph_device).  neighbors: counts[8 i + j] = T of neighbour j of key i (j = y: x[1:] + y,
+// j = 4 + y: y + x[:-1], canonicalised; layout as for QueryOps::lookup, but the strand of a
+// KC_KEYS_DUMP key is kept).  graph: two sweeps of the table on s -- the edge byte of every slot
+// into edges (nbuckets * S bytes), then per node (lo <= T(c) <= hi, hi 0 = no upper bound) its link
+// bits, its record {W key words, T(c) | flags << 32} (records == nullptr: none; only the first
+// `capacity` are written) and the statistics: stats (11 words, zeroed by the caller) receives the
+// ten words of kc_graph_stats, word 10 is the record cursor.  Both only read the table.
+template <int W>
+struct GraphOps {
+    static hipError_t neighbors(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
+                                uint32_t* counts, hipStream_t s);
+    static hipError_t graph(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, uint8_t* edges,
+                            uint64_t* records, uint64_t capacity, unsigned long long* stats, hipStream_t s);
+};
+constexpr int GRAPH_STAT_WORDS = 11;
+hipError_t launch_neighbors(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
+                            uint32_t* counts, hipStream_t s);
+hipError_t launch_graph(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, uint8_t* edges, uint64_t* records,
+                        uint64_t capacity, unsigned long long* stats, hipStream_t s);
+
 // Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
-// JoinOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// JoinOps, GraphOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

@@ -1,7 +1,8 @@
 // kc_util.hip -- small device helpers: the device XXH64 of the reference-layout Bloom
 // passes (kc_common.h xxh64_u64) over host-given inputs (test hook), the chunk checksum of
 // the partition reuse, the sharded Bloom filter's merge and filter-2 bit count, and the
-// W-dispatch of the table queries (kc_query_w.hip) and of the table algebra (kc_join_w.hip).
+// W-dispatch of the table queries (kc_query_w.hip), of the table algebra (kc_join_w.hip) and of
+// the de Bruijn graph kernels (kc_graph_w.hip).
 #include "kc_common.h"
 
 namespace kc {
@@ -167,6 +168,16 @@ hipError_t launch_join(TableView x, TableView y, TableView dst, int mode_x, int 
                        uint32_t y_min, uint32_t y_max, int op, int second, DevCounters* ctr, unsigned long long* stats,
                        hipStream_t s) {
     KC_DISPATCH(JoinOps, x.W, join(x, y, dst, mode_x, mode_y, x_min, x_max, y_min, y_max, op, second, ctr, stats, s));
+}
+
+// W-dispatch of the de Bruijn graph kernels (kc_graph_w.hip, one translation unit per key width)
+hipError_t launch_neighbors(TableView t, int k, int count_mode, int layout, const uint64_t* keys, uint64_t n,
+                            uint32_t* counts, hipStream_t s) {
+    KC_DISPATCH(GraphOps, t.W, neighbors(t, k, count_mode, layout, keys, n, counts, s));
+}
+hipError_t launch_graph(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, uint8_t* edges, uint64_t* records,
+                        uint64_t capacity, unsigned long long* stats, hipStream_t s) {
+    KC_DISPATCH(GraphOps, t.W, graph(t, k, count_mode, lo, hi, edges, records, capacity, stats, s));
 }
 
 }  // namespace kc

@@ -62,7 +62,11 @@ EXPORTS = (
     "kc_text_counts_device", "kc_text_counts", "kc_seq_stats_device", "kc_seq_stats",
     "kc_table_op_device", "kc_table_op",
     "kc_correct_device", "kc_correct",
+    "kc_neighbors_device", "kc_neighbors", "kc_graph_device", "kc_graph",
 )
+# kc_graph* node flags (KC_GRAPH_*): bits 0-7 the edges -- bit y: canon(c[1:] + y) is a node (side
+# R), bit 4 + y: canon(y + c[:-1]) is a node (side L) -- then the two unitig links and the node bit
+GRAPH_LINK_R, GRAPH_LINK_L, GRAPH_NODE = 0x0100, 0x0200, 0x8000
 # kc_table_op* operations (KC_OP_*): on the raw counts ca, cb of a key in a and in b
 OP_INTERSECT_MIN, OP_INTERSECT_SUM, OP_INTERSECT_LEFT, OP_SUBTRACT, OP_COUNTS_SUBTRACT, OP_UNION_SUM, OP_UNION_MAX = range(7)
 OP_NAMES = {"intersect-min": OP_INTERSECT_MIN, "intersect-sum": OP_INTERSECT_SUM, "intersect-left": OP_INTERSECT_LEFT,
@@ -117,6 +121,18 @@ class kc_op_stats(ctypes.Structure):  # 40 bytes
 
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_graph_stats(ctypes.Structure):  # 80 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("nodes", "edge_ends", "link_ends", "isolated", "palindromes")] + \
+               [("side_degree", ctypes.c_uint64 * 5)]
+
+    def as_dict(self) -> dict:
+        """the ten statistics, side_degree as a list, plus open_unitigs = nodes - link_ends / 2"""
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_[:5]}
+        d["side_degree"] = [int(x) for x in self.side_degree]
+        d["open_unitigs"] = d["nodes"] - d["link_ends"] // 2
+        return d
 
 
 class kc_correct_stat(ctypes.Structure):  # 16 bytes
@@ -227,6 +243,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_correct": (I32, [P, P, U64, P, U64, ctypes.c_uint32, P, P]),
         "kc_table_op_device": (I32, [P, P, P, ctypes.POINTER(kc_op_desc), P, P]),
         "kc_table_op": (I32, [P, P, P, ctypes.POINTER(kc_op_desc), ctypes.POINTER(kc_op_stats)]),
+        "kc_neighbors_device": (I32, [P, P, U64, I32, P, P]),
+        "kc_neighbors": (I32, [P, P, U64, I32, P]),
+        "kc_graph_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, P, P]),
+        "kc_graph": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(U64)),
+                           ctypes.POINTER(U64), ctypes.POINTER(kc_graph_stats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -747,6 +768,60 @@ class KmerCounter:
         (of those, in b), b_only (UNION ops only), out_keys and out_sum (the records added here)."""
         d, st = _op_desc(op, a_range, b_range), kc_op_stats()
         self._chk(self.lib.kc_table_op(self._ctx, a._ctx, b._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_table_op")
+        return st.as_dict()
+
+    # -- the de Bruijn graph of the counted table (kc_neighbors*, kc_graph*)
+    def neighbors_device(self, keys_ptr: int, n: int, out_ptr: int, table_keys: bool = False, stream: int = 0):
+        """T(c) of the eight neighbours of n keys in device memory (W uint64 each, as lookup_device
+        takes them; the strand of a dump-layout key is kept) into 8 uint32 per key at out_ptr:
+        [y] = canon(x[1:] + y), [4 + y] = canon(y + x[:-1]); enqueued on `stream`, no wait."""
+        self._chk(self.lib.kc_neighbors_device(self._ctx, ctypes.c_void_p(keys_ptr or None), n,
+                                               KEYS_TABLE if table_keys else KEYS_DUMP,
+                                               ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)),
+                  "kc_neighbors_device")
+
+    def neighbors(self, keys: np.ndarray, table_keys: bool = False) -> np.ndarray:
+        """T(c) of the eight neighbours of keys (n, W) uint64 (encode_kmers' layout, the strand as
+        given; or table keys) as an (n, 8) uint32 array: column y the k-mer that follows with base y
+        appended, column 4 + y the one that precedes with base y prepended; 0 = absent."""
+        W = self.lib.kc_key_words(self._ctx)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, W)
+        out = np.zeros((k.shape[0], 8), dtype=np.uint32)
+        self._chk(self.lib.kc_neighbors(self._ctx, k.ctypes.data, k.shape[0], KEYS_TABLE if table_keys else KEYS_DUMP,
+                                        out.ctypes.data), "kc_neighbors")
+        return out
+
+    def graph_device(self, min_count: int = 1, max_count: int = 0, records_ptr: int = 0, capacity: int = 0,
+                     n_ptr: int = 0, stats_ptr: int = 0, stream: int = 0):
+        """The graph of the k-mers with min_count <= T(c) <= max_count (0: no upper bound), all in
+        device memory: W + 1 uint64 per node at records_ptr (0: none; at most `capacity` are
+        written), the number of nodes at n_ptr and the 80-byte kc_graph_stats at stats_ptr (0: none);
+        enqueued on `stream`, no wait."""
+        self._chk(self.lib.kc_graph_device(self._ctx, min_count, max_count, ctypes.c_void_p(records_ptr or None),
+                                           capacity, ctypes.c_void_p(n_ptr or None), ctypes.c_void_p(stats_ptr or None),
+                                           ctypes.c_void_p(stream or None)), "kc_graph_device")
+
+    def graph(self, min_count: int = 1, max_count: int = 0) -> Tuple[np.ndarray, dict]:
+        """(records, statistics) of the de Bruijn graph whose nodes are the k-mers with min_count <=
+        T(c) <= max_count: records (n, W + 1) uint64, the key words as dump() and then T(c) | flags <<
+        32 (flags: GRAPH_*); the statistics as graph_stats()."""
+        p = ctypes.POINTER(ctypes.c_uint64)()
+        n, st = ctypes.c_uint64(), kc_graph_stats()
+        self._chk(self.lib.kc_graph(self._ctx, min_count, max_count, ctypes.byref(p), ctypes.byref(n), ctypes.byref(st)),
+                  "kc_graph")
+        W = self.lib.kc_key_words(self._ctx)
+        try:
+            arr = (np.ctypeslib.as_array(p, shape=(n.value * (W + 1),)).copy() if n.value
+                   else np.zeros(0, dtype=np.uint64))
+        finally:
+            self.lib.kc_free(p)
+        return arr.reshape(-1, W + 1), st.as_dict()
+
+    def graph_stats(self, min_count: int = 1, max_count: int = 0) -> dict:
+        """The graph's statistics without its records: nodes, edge_ends, link_ends, isolated,
+        palindromes, side_degree[0..4] and open_unitigs (the non-circular unitigs)."""
+        st = kc_graph_stats()
+        self._chk(self.lib.kc_graph(self._ctx, min_count, max_count, None, None, ctypes.byref(st)), "kc_graph")
         return st.as_dict()
 
     def compact_read(self, info: dict):

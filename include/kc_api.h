@@ -499,6 +499,76 @@ int kc_table_op_device(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, 
                        void* hip_stream);
 int kc_table_op(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, kc_op_stats* stats);
 
+/* The de Bruijn graph of the counted table: what comes next.  A counted k-mer set IS a de Bruijn
+ * graph, and assembly, tip and bubble statistics, seed extension and repeat detection ask it for a
+ * k-mer's neighbours; the reference's users rebuild a hash table from the output text for that.
+ * Here the table's keys give their k-mers back, every neighbour is one probe, and no key leaves HBM.
+ * Strings are over ACGT with codes A 0, C 1, G 2, T 3; rc is the reverse complement, canon(z) =
+ * min(z, rc(z)); T is kc_lookup's count (-a is applied nowhere).  A range is min_count (0 means 1)
+ * and max_count (0 = no upper bound), as in kc_op_desc.
+ *   node          a canonical k-mer c the table holds with min_count <= T(c) <= max_count.
+ *   edges of c    8 bits: bit y is set when canon(c[1:] + y) is a node (side R), bit 4 + y when
+ *                 canon(y + c[:-1]) is a node (side L); deg_R and deg_L are the popcounts of the
+ *                 two nibbles.  (c may be its own neighbour: AAA...A, a hairpin x -> rc(x).)
+ *   facing side   side R, z = c[1:] + y, d = canon(z): c sits on d's side L if d == z, else on d's
+ *                 side R; side L, z = y + c[:-1]: on d's side R if d == z, else on d's side L.
+ *   link(c, s)    deg_s(c) == 1, its one neighbour d != c, neither c nor d is its own reverse
+ *                 complement (even k only), and the degree of d's facing side is 1.  Links are
+ *                 mutual: link(c, s) holds exactly when link(d, facing side) does, and that one
+ *                 leads back to (c, s).  Every maximal path of links is a unitig; the non-circular
+ *                 unitigs number nodes - link_ends / 2.
+ *   flags         16 bits per node: bits 0-7 the edges, KC_GRAPH_LINK_R, KC_GRAPH_LINK_L,
+ *                 KC_GRAPH_NODE (always set); every other bit 0.
+ *   kc_neighbors_device  counts[8 i + y] = T(canon(x[1:] + y)), counts[8 i + 4 + y] =
+ *                 T(canon(y + x[:-1])), 0 = absent, x = key i (kc_key_words() words each).
+ *                 KC_KEYS_DUMP: x is the k-mer as given -- the strand is respected, so the other
+ *                 strand's answer has R and L swapped and complemented; a key with a bit above
+ *                 2k - 1 answers eight zeros.  KC_KEYS_TABLE: x is the canonical k-mer the table
+ *                 key encodes; word 0 == 0 answers zeros.  No range is applied.
+ *   kc_neighbors  the same for host arrays; waits for the answer.
+ *   kc_graph_device  one record per node, kc_key_words() + 1 words: the key in kc_dump's layout,
+ *                 then T(c) | (uint64_t)flags << 32; the record order is unspecified, like
+ *                 kc_write's lines.  dev_records == NULL gives the statistics only.
+ *                 *dev_n_records is always the number of nodes; only the first `capacity` records
+ *                 are written and nothing is written past them (kc_stats.distinct always suffices
+ *                 as capacity).  dev_stats and dev_n_records (device memory) may be NULL.  Two
+ *                 sweeps of the table: the first probes every node's eight neighbours and keeps one
+ *                 edge byte per table slot in scratch of the context (kc_stats.table_slots bytes),
+ *                 the second finds the links from those bytes, reduces the statistics and appends
+ *                 the records.
+ *   kc_graph      the same with the records (free with kc_free) and the statistics in host
+ *                 memory; records, n_records and stats may each be NULL (records == NULL or
+ *                 n_records == NULL: statistics only); waits.
+ * The *_device forms follow the *_device rule as kc_lookup_device does: staged host chunks are
+ * flushed first, the work runs on hip_stream after what is queued there and after the context's
+ * own stream, and the context's later work follows it; no host wait (the first kc_graph_device on a
+ * table allocates the edge scratch).  An emptied table (kc_reset, kc_clear_table) has no nodes and
+ * kc_neighbors* answers zeros.  KC_ERR_STATE: no table (a Bloom context before kc_bloom_finalize)
+ * or a job a failed pass left incomplete.  KC_ERR_ARG: k < 2, min_count above a non-zero max_count,
+ * a NULL key or count array with n_keys > 0, an unknown layout.  n_keys == 0 is KC_OK.  Any table
+ * answers: Bloom-gated, merged, counted by a deferred level 3, any mode.  The table is only read
+ * and no counter of kc_stats changes. */
+#define KC_GRAPH_EDGE_R(y) (1u << (y))        /* canon(c[1:] + y) is a node */
+#define KC_GRAPH_EDGE_L(y) (1u << (4 + (y)))  /* canon(y + c[:-1]) is a node */
+#define KC_GRAPH_LINK_R 0x0100u  /* link(c, R) */
+#define KC_GRAPH_LINK_L 0x0200u  /* link(c, L) */
+#define KC_GRAPH_NODE   0x8000u  /* set in every record */
+typedef struct {          /* 80 bytes */
+    uint64_t nodes;           /* nodes */
+    uint64_t edge_ends;       /* set edge bits (an edge between two nodes counts at both ends) */
+    uint64_t link_ends;       /* set link bits (even: links are mutual) */
+    uint64_t isolated;        /* nodes with both degrees 0 */
+    uint64_t palindromes;     /* nodes with c == rc(c) */
+    uint64_t side_degree[5];  /* node sides with degree 0..4; sums to 2 * nodes */
+} kc_graph_stats;
+int kc_neighbors_device(kc_ctx* ctx, const uint64_t* dev_keys, uint64_t n_keys, int key_layout,
+                        uint32_t* dev_counts /* 8 per key */, void* hip_stream);
+int kc_neighbors(kc_ctx* ctx, const uint64_t* keys, uint64_t n_keys, int key_layout, uint32_t* counts);
+int kc_graph_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, uint64_t* dev_records, uint64_t capacity,
+                    uint64_t* dev_n_records, kc_graph_stats* dev_stats, void* hip_stream);
+int kc_graph(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, uint64_t** records, uint64_t* n_records,
+             kc_graph_stats* stats);
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
