@@ -1,0 +1,153 @@
+// kc_api_unitig.cpp -- the unitigs of the counted table's de Bruijn graph (include/kc_api.h
+// kc_unitigs*): the checks, the scratch and the host form.  Kernels: kc_unitig_impl.h (the sweeps
+// that number the nodes and find the successor states, the bases) and kc_unitig.hip (the ranking,
+// the cut of the circles, the records); the host arithmetic: kc_unitig_host.h.
+#include "kc_ctx.h"
+
+#pragma GCC visibility push(hidden)
+
+static_assert(sizeof(kc_unitig) == 32 && sizeof(kc_unitig_stats) == 40, "include/kc_api.h states these sizes");
+static_assert(sizeof(kc_unitig_stats) == 5 * sizeof(unsigned long long), "UC_STATS: five control words");
+static_assert(sizeof(UnitigState) * 4 + 4 + 8 + 8 + 4 + 4 + 16 == UNITIG_NODE_BYTES, "kc_unitig_host.h counts a node's bytes");
+
+static int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count) {
+    if (c->cfg.k < 2) return c->fail(KC_ERR_ARG, "unitigs need k >= 2");
+    if (max_count && min_count > max_count) return c->fail(KC_ERR_ARG, "kc_unitigs: min_count is above max_count");
+    JOB_OK(c);
+    if (!c->nbuckets) return c->fail(KC_ERR_STATE, "no table (kc_bloom_finalize must precede a unitig query)");
+    return KC_OK;
+}
+
+UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound) {
+    const UnitigLayout l = unitig_layout(bound);
+    uint64_t* b = c->d_unitig_node;
+    UnitigBufs u{};
+    u.edges = c->d_graph_edges;
+    u.id_of_slot = c->d_unitig_ids;
+    u.bound = bound;
+    u.st[0] = reinterpret_cast<UnitigState*>(b + l.st0);
+    u.st[1] = reinterpret_cast<UnitigState*>(b + l.st1);
+    u.slot_of = b + l.slot_of;
+    u.off = b + l.off;
+    u.succ = reinterpret_cast<uint32_t*>(b + l.succ);
+    u.tc = reinterpret_cast<uint32_t*>(b + l.tc);
+    u.start = reinterpret_cast<uint32_t*>(b + l.start);
+    u.pos = reinterpret_cast<uint32_t*>(b + l.pos);
+    u.ctl = c->d_unitig_ctl;
+    return u;
+}
+
+// The ranking on s for up to `bound` nodes (the caller has joined s): the scratch first -- a failure
+// is reported before any kernel of the call is launched -- then the three sweeps and the jump
+// launches.  Leaves the views and the rounds for unitig_write.
+static int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u,
+                       int* rounds) {
+    const uint64_t slots = c->nbuckets * (uint64_t)c->S;
+    bound = std::max<uint64_t>(1, std::min(bound, slots));
+    if (bound >= UNITIG_MAX_BOUND)
+        return c->fail(KC_ERR_NOMEM, "kc_unitigs: " + std::to_string(bound) + " node ids do not fit 32-bit states (the "
+                                     "device form sizes by the table's slots, kc_unitigs by the k-mers from min_count on)");
+    const uint64_t words = unitig_layout(bound).words;
+    if (c->d_graph_edges.capacity() < slots || c->d_unitig_ids.capacity() < slots || c->d_unitig_node.capacity() < words)
+        make_room(c, unitig_scratch_bytes(slots, bound));
+    if (!c->d_graph_edges.reserve(slots) || !c->d_unitig_ids.reserve(slots) || !c->d_unitig_node.reserve(words) ||
+        !c->d_unitig_ctl.reserve(UNITIG_CTL_WORDS))
+        return c->fail(KC_ERR_NOMEM, "kc_unitigs: scratch allocation failed (" +
+                                     std::to_string(unitig_scratch_bytes(slots, bound)) + " bytes)");
+    *u = unitig_bufs(c, bound);
+    *rounds = unitig_rounds(bound);
+    HIPCHK(c, hipMemsetAsync(u->ctl, 0, UNITIG_CTL_WORDS * sizeof(unsigned long long), s));
+    HIPCHK(c, launch_unitig_succ(table_view(c), c->cfg.k, c->cfg.mode == 0 ? 0 : 1, min_count ? min_count : 1, max_count,
+                                 *u, s));
+    HIPCHK(c, launch_unitig_rank(*u, *rounds, s));
+    return KC_OK;
+}
+
+// the records, the bases and the statistics of a ranking, each where its pointer is not NULL
+static int unitig_write(kc_ctx* c, const UnitigBufs& u, int rounds, kc_unitig* recs, uint64_t cap_unitigs, uint8_t* bases,
+                        uint64_t cap_bases, kc_unitig_stats* dev_stats, hipStream_t s) {
+    HIPCHK(c, launch_unitig_heads(u, c->cfg.k, rounds, recs, cap_unitigs, bases ? cap_bases : 0, s));
+    if (bases) HIPCHK(c, launch_unitig_emit(table_view(c), c->cfg.k, u, bases, s));
+    if (dev_stats)
+        HIPCHK(c, hipMemcpyAsync(dev_stats, u.ctl + UC_STATS, sizeof(kc_unitig_stats), hipMemcpyDeviceToDevice, s));
+    return KC_OK;
+}
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int kc_unitigs_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs, uint64_t cap_unitigs,
+                      uint8_t* bases, uint64_t cap_bases, kc_unitig_stats* stats, void* sp) {
+    if (!c) return KC_ERR_ARG;
+    int rc = unitig_check(c, min_count, max_count);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)sp;
+    if ((rc = flush_host(c))) return rc;
+    StreamScope on(c, s);
+    if ((rc = on.join())) return rc;
+    if ((rc = materialize_zero(c, s))) return rc;  // an emptied table has no unitigs
+    UnitigBufs u;
+    int rounds = 0;
+    // no host wait, so the ids are sized by what the host knows: the table's slots
+    if ((rc = unitig_rank(c, min_count, max_count, c->nbuckets * (uint64_t)c->S, s, &u, &rounds))) return rc;
+    if ((rc = unitig_write(c, u, rounds, unitigs, cap_unitigs, bases, cap_bases, stats, s))) return rc;
+    return on.finish();
+}
+
+int kc_unitigs(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+               kc_unitig_stats* stats) {
+    if (!c) return KC_ERR_ARG;
+    if (unitigs) *unitigs = nullptr;
+    if (bases) *bases = nullptr;
+    int rc = unitig_check(c, min_count, max_count);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    // the ids' bound: the k-mers with T(c) >= min_count (one count-only sweep, as kc_graph's)
+    unsigned long long bound = 0;
+    if ((rc = sync_for_read(c))) return rc;
+    HIPCHK(c, hipMemsetAsync(&c->d_ctr->dump_n, 0, 16 * 8 * 2, s));  // dump_n + occupied lines
+    HIPCHK(c, launch_dump(table_view(c), c->cfg.mode == 0 ? 0 : 1, min_count ? min_count : 1, nullptr, c->d_ctr, s));
+    HIPCHK(c, hipMemcpyAsync(&bound, &c->d_ctr->dump_n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    // rank once, read the totals, allocate, write
+    UnitigBufs u;
+    int rounds = 0;
+    kc_unitig_stats h{};
+    DevBuf<kc_unitig> dr;
+    DevBuf<uint8_t> db;
+    DrainOnError drain{s};
+    if ((rc = unitig_rank(c, min_count, max_count, bound, s, &u, &rounds))) return rc;
+    if ((rc = unitig_write(c, u, rounds, nullptr, 0, nullptr, 0, nullptr, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(&h, u.ctl + UC_STATS, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const bool want_r = unitigs && h.unitigs, want_b = bases && h.bases;
+    if (want_r || want_b) {
+        make_room(c, h.unitigs * sizeof(kc_unitig) + h.bases);
+        if ((want_r && !dr.reserve(h.unitigs)) || (want_b && !db.reserve(h.bases)))
+            return c->fail(KC_ERR_NOMEM, "kc_unitigs: record and base buffer allocation failed");
+        if ((rc = unitig_write(c, u, rounds, want_r ? dr.get() : nullptr, h.unitigs, want_b ? db.get() : nullptr, h.bases,
+                               nullptr, s)))
+            return rc;
+    }
+    std::unique_ptr<kc_unitig, StdFree> out_r;
+    std::unique_ptr<uint8_t, StdFree> out_b;
+    if (unitigs) {
+        out_r.reset((kc_unitig*)std::malloc(std::max<size_t>(1, h.unitigs * sizeof(kc_unitig))));
+        if (!out_r) return c->fail(KC_ERR_NOMEM, "host allocation failed");
+        if (want_r) HIPCHK(c, hipMemcpyAsync(out_r.get(), dr, h.unitigs * sizeof(kc_unitig), hipMemcpyDeviceToHost, s));
+    }
+    if (bases) {
+        out_b.reset((uint8_t*)std::malloc(std::max<size_t>(1, h.bases)));
+        if (!out_b) return c->fail(KC_ERR_NOMEM, "host allocation failed");
+        if (want_b) HIPCHK(c, hipMemcpyAsync(out_b.get(), db, h.bases, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    drain.done();
+    if (unitigs) *unitigs = out_r.release();
+    if (bases) *bases = out_b.release();
+    if (stats) *stats = h;
+    return KC_OK;
+}
+
+}  // extern "C"

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/kc_api.h"
+#include "kc_unitig_host.h"
 
 namespace {
 
@@ -85,6 +86,11 @@ struct Args {
     std::string graph, graph_stats;
     unsigned long long graph_min = 0, graph_max = 0;
     bool graph_min_set = false, graph_max_set = false;
+    // --unitigs FILE [--unitigs-min N] [--unitigs-max N]: the unitigs of that graph (kc_unitigs) as
+    // FASTA, a record per unitig; the range as for --graph
+    std::string unitigs;
+    unsigned long long unitigs_min = 0, unitigs_max = 0;
+    bool unitigs_min_set = false, unitigs_max_set = false;
 };
 
 const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
@@ -130,7 +136,13 @@ void usage(const char* prog) {
                  "  --graph-min,--graph-max UINT\n"
                  "                              a k-mer is a node when its count is in this range (def. the -a value and\n"
                  "                              up); needs --graph\n"
-                 "  --graph-stats FILE          write the graph's statistics as \"<name> <value>\" lines\n\n"
+                 "  --graph-stats FILE          write the graph's statistics as \"<name> <value>\" lines\n"
+                 "  --unitigs FILE              write the unitigs of that graph as FASTA, a record per unitig:\n"
+                 "                              \">i LN:i:<bases> KC:i:<sum of counts> km:f:<mean count>\", then\n"
+                 "                              \" circular\" for a circle, and the bases on one line\n"
+                 "  --unitigs-min,--unitigs-max UINT\n"
+                 "                              a k-mer is a node when its count is in this range (def. the -a value and\n"
+                 "                              up); needs --unitigs\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -332,6 +344,13 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 (o == "--graph-min" ? a->graph_min : a->graph_max) = u;
                 (o == "--graph-min" ? a->graph_min_set : a->graph_max_set) = true;
+            } else if (o == "--unitigs") {
+                a->unitigs = v;
+            } else if (o == "--unitigs-min" || o == "--unitigs-max") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                (o == "--unitigs-min" ? a->unitigs_min : a->unitigs_max) = u;
+                (o == "--unitigs-min" ? a->unitigs_min_set : a->unitigs_max_set) = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -387,6 +406,11 @@ int parse(int argc, char** argv, Args* a) {
     if (!a->graph_min_set) a->graph_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
     if (a->graph_max && a->graph_min > a->graph_max)
         return cli_error(kValidation, "--graph-min: a minimum above its maximum");
+    if ((a->unitigs_min_set || a->unitigs_max_set) && a->unitigs.empty())
+        return cli_error(kRequires, "--unitigs-min/--unitigs-max require --unitigs");
+    if (!a->unitigs_min_set) a->unitigs_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if (a->unitigs_max && a->unitigs_min > a->unitigs_max)
+        return cli_error(kValidation, "--unitigs-min: a minimum above its maximum");
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -1289,6 +1313,28 @@ int main(int argc, char** argv) {
         std::cout << "De Bruijn graph: " << gst.nodes << " nodes, " << gst.edge_ends << " edge ends, " << gst.link_ends
                   << " link ends, " << open_unitigs << " open unitigs\n";
     }
+    if (!a.unitigs.empty()) {  // extension: the unitigs of that graph, as FASTA
+        kc_unitig* urec = nullptr;
+        uint8_t* ubases = nullptr;
+        kc_unitig_stats ust;
+        if (kc_unitigs(ctx, (uint32_t)a.unitigs_min, (uint32_t)a.unitigs_max, &urec, &ubases, &ust) != KC_OK) die("unitigs");
+        FILE* f = std::fopen(a.unitigs.c_str(), "w");
+        if (!f) { std::cerr << "cannot write " << a.unitigs << std::endl; kc_free(urec); kc_free(ubases); kc_destroy(ctx); return 1; }
+        char head[160];
+        for (uint64_t i = 0; i < ust.unitigs; i++) {
+            const kc_unitig& r = urec[i];
+            kc::unitig_fasta_header(head, sizeof head, i, r.n_nodes, r.count_sum, (int)a.k, r.flags & KC_UNITIG_CIRCULAR);
+            std::fputs(head, f);
+            std::fputc('\n', f);
+            std::fwrite(ubases + r.offset, 1, (size_t)(r.n_nodes + (uint64_t)a.k - 1), f);
+            std::fputc('\n', f);
+        }
+        kc_free(urec);
+        kc_free(ubases);
+        if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.unitigs << std::endl; kc_destroy(ctx); return 1; }
+        std::cout << "Unitigs: " << ust.unitigs << " (" << ust.circular << " circular), " << ust.nodes << " nodes, "
+                  << ust.bases << " bases, longest " << ust.max_nodes << " nodes\n";
+    }
     auto t3 = clk::now();
     std::cout << "Time used to build hash table: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() + (a.use_bf ? 0 : prep_us)
@@ -1300,7 +1346,7 @@ int main(int argc, char** argv) {
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
     if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty() || !a.graph.empty() ||
-        !a.graph_stats.empty())
+        !a.graph_stats.empty() || !a.unitigs.empty())
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
                   << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")

@@ -17,6 +17,7 @@
 
 #include "../../include/kc_api.h"
 #include "kc_internal.h"
+#include "kc_unitig_host.h"
 
 // (nothing declared here is an export of libkc.so)
 #pragma GCC visibility push(hidden)
@@ -247,6 +248,11 @@ struct kc_ctx {
     // followed by the record cursor (GRAPH_STAT_WORDS)
     DevBuf<uint8_t> d_graph_edges;
     DevBuf<unsigned long long> d_graph_stat;
+    // the unitigs (kc_api_unitig.cpp): a node id per table slot, the per-node arrays of UnitigBufs in
+    // one block (unitig_layout), the control words; they grow only
+    DevBuf<uint32_t> d_unitig_ids;
+    DevBuf<uint64_t> d_unitig_node;
+    DevBuf<unsigned long long> d_unitig_ctl;
 
     uint64_t n_chunks = 0, n_bytes = 0;
 
@@ -458,6 +464,8 @@ bool use_partitioned_bloom(const kc_ctx* c, uint64_t syms);
 int sync_for_read(kc_ctx* c);
 void make_room(kc_ctx* c, uint64_t bytes);
 void drop_compact(kc_ctx* c);
+// kc_api_unitig.cpp
+UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound);
 // kc_api_pass.cpp
 int flush_host(kc_ctx* c);
 int device_pass(kc_ctx* c, const uint8_t* img, const kc_chunk* chunks, size_t n, int fmt, int pass, hipStream_t s);

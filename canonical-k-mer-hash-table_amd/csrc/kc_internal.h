@@ -504,9 +504,70 @@ hipError_t launch_neighbors(TableView t, int k, int count_mode, int layout, cons
 hipError_t launch_graph(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, uint8_t* edges, uint64_t* records,
                         uint64_t capacity, unsigned long long* stats, hipStream_t s);
 
-// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
-// JoinOps, GraphOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// The unitigs of that graph (kc_unitig_impl.h, kc_unitig.hip; the definitions: include/kc_api.h
+// kc_unitigs_device).  Nodes get dense ids, a directed state is 2 * id + exit side (0 = R, 1 = L),
+// and list ranking by pointer jumping gives every state the end of its path, its distance to it and
+// the counts on the way.  One state of one of the two ping-pong buffers:
+struct alignas(8) UnitigState {
+    uint32_t nxt;    // the state pointed at; UNITIG_DONE set: it is the path's end (an end points at itself)
+    uint32_t dist;   // hops to nxt
+    uint64_t sum;    // T(c) over the nodes of those hops (the node of nxt included, this state's not)
+    uint32_t mn;     // least node id over the states [this, nxt); UNITIG_CIRC: the cut of a circle
+    uint32_t stamp;  // launch + 1 that wrote the DONE value here (the next one copies it across), 0: both buffers hold it
+};
+static_assert(sizeof(UnitigState) == 24, "kc_unitig_host.h counts 24 bytes a state and buffer");
+constexpr uint32_t UNITIG_DONE = 0x80000000u, UNITIG_END = 0xFFFFFFFFu, UNITIG_CIRC = 0xFFFFFFFFu;
+constexpr uint32_t UNITIG_NO_ID = 0xFFFFFFFFu;
+constexpr uint64_t UNITIG_NO_OFF = ~0ULL;
+// the control words (device, zeroed per call): counters, then per jump launch j the source buffer
+// UC_SRC + j (launch j writes j + 1's) and "a state moved" UC_MOVED + j
+constexpr int UNITIG_MAX_LAUNCHES = 66;  // two rankings of at most 32 rounds, and the slot one past the last
+enum : int {
+    UC_NODES = 0,   // the node cursor: the number of nodes
+    UC_CYCLE,       // states the first ranking left on cycles
+    UC_REC,         // record cursor
+    UC_BASE,        // base cursor
+    UC_STATS,       // the five words of kc_unitig_stats (up to UC_STATS + 4)
+    UC_SRC = 16,
+    UC_MOVED = UC_SRC + UNITIG_MAX_LAUNCHES,
+    UNITIG_CTL_WORDS = UC_MOVED + UNITIG_MAX_LAUNCHES
+};
+struct UnitigBufs {
+    uint8_t* edges;        // table_slots edge bytes (the graph layer's scratch)
+    uint32_t* id_of_slot;  // table_slots
+    uint64_t bound;        // the node ids that fit: every array below is sized by it
+    uint32_t* tc;          // [id] T(c)
+    uint64_t* slot_of;     // [id]
+    uint32_t* succ;        // [2 id + side] the successor state, UNITIG_END: none
+    UnitigState* st[2];    // [2 id + side], ping and pong
+    uint32_t* start;       // [id] the id of its unitig's first node
+    uint32_t* pos;         // [id] its position | read on the reverse strand << 31
+    uint64_t* off;         // [2 start id] the unitig's base offset, UNITIG_NO_OFF: its bases do not fit; [+ 1] its nodes
+    unsigned long long* ctl;  // UNITIG_CTL_WORDS
+};
+// the nodes the sweep numbered, never more than the ids that fit
+__device__ inline uint64_t unitig_nodes(const UnitigBufs& u) {
+    const unsigned long long n = u.ctl[UC_NODES];
+    return n < u.bound ? n : u.bound;
+}
+template <int W>
+struct UnitigOps {
+    // edges, dense ids, successors and the first states (three sweeps of the table)
+    static hipError_t succ(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, UnitigBufs u, hipStream_t s);
+    // every node's base(s) into bases, bounded per unitig by what k_unitig_heads left in u.off
+    static hipError_t emit(TableView t, int k, UnitigBufs u, uint8_t* bases, hipStream_t s);
+};
+hipError_t launch_unitig_succ(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, UnitigBufs u, hipStream_t s);
+hipError_t launch_unitig_emit(TableView t, int k, UnitigBufs u, uint8_t* bases, hipStream_t s);
+// kc_unitig.hip, no key width: `rounds` jump launches, the cut of the circles, `rounds` more
+hipError_t launch_unitig_rank(UnitigBufs u, int rounds, hipStream_t s);
+// records (nullptr: none), offsets and statistics; zeroes its cursors first
+hipError_t launch_unitig_heads(UnitigBufs u, int k, int rounds, void* records, uint64_t cap_unitigs, uint64_t cap_bases,
+                               hipStream_t s);
+
+// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip, kc_unitig.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
+// JoinOps, GraphOps, UnitigOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

@@ -1,0 +1,210 @@
+// kc_unitig_impl.h -- the unitigs of the counted table's de Bruijn graph, the kernels that touch a
+// key, for one key width W (instantiated by kc_unitig_w.hip; the definitions: include/kc_api.h
+// kc_unitigs_device; the ranking between them: kc_unitig.hip).
+//
+//   k_graph_edges    (kc_graph_impl.h, as it is) the edge byte of every slot.
+//   k_unitig_number  sweeps the table and gives every node a dense id behind one cursor, one atomic
+//                    per workgroup and tile as k_graph_links takes its records' places: id_of_slot
+//                    (UNITIG_NO_ID for every other slot), tc[id] = T(c), slot_of[id].
+//   k_unitig_succ    a second sweep (a partner's tile may be numbered later, so its id is only known
+//                    now): the link rule of k_graph_links for both sides of a node, and for the state
+//                    (id, side) its successor (partner's id, the other side of the facing side) or
+//                    UNITIG_END, and its first UnitigState.  A partner id at or above the node count
+//                    becomes UNITIG_END here, so no later kernel follows a wild pointer.
+//   k_unitig_emit    every node rebuilds its k-mer from its slot and writes the last base of the
+//                    strand it is read on at offset + k - 1 + position; the node at position 0 writes
+//                    all k.  A unitig whose bases do not fit has UNITIG_NO_OFF for an offset.
+//
+// Plain loads of the table, no atomics on it, every probe bounded by BPR; every store index is a
+// cursor value below `bound`, an id below the node count, or an offset k_unitig_heads bounded.
+#pragma once
+#include "kc_graph_impl.h"
+
+namespace kc {
+
+struct UnitigArgs {
+    TableView tv;
+    int k, count_mode;
+    uint32_t lo, hi;
+    UnitigBufs u;
+};
+
+// the ASCII base of the code in the two lowest bits
+DEV uint8_t unitig_base(uint64_t c) { return (uint8_t)(0x54474341u >> (8 * ((uint32_t)c & 3))); }
+
+template <int W>
+__global__ __launch_bounds__(GRAPH_T) void k_unitig_number(UnitigArgs g) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __shared__ uint32_t s_tc[GRAPH_RPT][GRAPH_T];  // T(c) of call r of thread t, 0: no node
+    __shared__ unsigned long long s_wt[GRAPH_T / 64], s_base;
+    uint32_t mine = 0;
+    uint64_t first_slot = 0;
+    constexpr uint64_t step = GRAPH_BUCKET_MAP ? 1 : GRAPH_T;
+    constexpr int S = BUCKET_WORDS / (W + 1);
+    graph_sweep<W, GRAPH_BUCKET_MAP>(
+        g.tv,
+        [&](bool in, uint64_t slot, const uint64_t (&tk)[W], uint64_t cw, int r) {
+            const uint32_t tc = tc_of(cw, g.count_mode);
+            const bool node = in && tk[0] != EMPTY && join_in_range(tc, g.lo, g.hi);
+            if (r == 0) first_slot = slot;
+            s_tc[r][threadIdx.x] = node ? tc : 0;  // (a node's T(c) is at least lo >= 1)
+            mine += node;
+            if (in && !node) g.u.id_of_slot[slot] = UNITIG_NO_ID;
+        },
+        [&] {
+            const uint32_t incl = wave_incl_sum(mine);
+            if (lane == 63) s_wt[wid] = incl;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                unsigned long long tot = 0;
+                for (int w = 0; w < GRAPH_T / 64; w++) tot += s_wt[w];
+                s_base = tot ? atomicAdd(g.u.ctl + UC_NODES, tot) : 0;
+            }
+            __syncthreads();
+            uint64_t id = s_base + incl - mine;
+            for (int w = 0; w < wid; w++) id += s_wt[w];
+            constexpr int RPT = GRAPH_BUCKET_MAP ? S : GRAPH_ITERS;
+#pragma unroll 1
+            for (int r = 0; r < RPT && mine; r++) {
+                const uint32_t tc = s_tc[r][threadIdx.x];
+                if (!tc) continue;
+                const uint64_t slot = first_slot + (uint64_t)r * step;
+                const bool fits = id < g.u.bound;
+                g.u.id_of_slot[slot] = fits ? (uint32_t)id : UNITIG_NO_ID;
+                if (fits) {
+                    g.u.tc[id] = tc;
+                    g.u.slot_of[id] = slot;
+                }
+                id++;
+            }
+            mine = 0;
+            __syncthreads();
+        });
+}
+
+template <int W>
+__global__ __launch_bounds__(GRAPH_T) void k_unitig_succ(UnitigArgs g) {
+    const RollConst rk = make_roll<W>(g.k, 0, 0);
+    const uint64_t n_nodes = unitig_nodes(g.u);
+    graph_sweep<W, GRAPH_BUCKET_MAP>(
+        g.tv,
+        [&](bool in, uint64_t slot, const uint64_t (&tk)[W], uint64_t cw, int) {
+            const uint32_t tc = tc_of(cw, g.count_mode);
+            if (!(in && tk[0] != EMPTY && join_in_range(tc, g.lo, g.hi))) return;
+            const uint32_t id = g.u.id_of_slot[slot];
+            if (id >= n_nodes) return;
+            uint64_t K[W], RC[W];
+            from_tkey<W>(tk, K);
+            revcomp<W>(K, rk, RC);
+            const bool pal = key_eq<W>(K, RC);
+            const uint32_t e = g.u.edges[slot];
+#pragma unroll 1
+            for (int side = 0; side < 2; side++) {
+                const uint32_t nib = (e >> (4 * side)) & 15;
+                uint32_t nx = UNITIG_END;
+                if (__popc(nib) == 1 && !pal) {  // the link rule, as k_graph_links has it
+                    uint64_t t[W];
+                    const int ori = neighbor_tkeys<W>(K, RC, 4 * side + (__ffs((int)nib) - 1), rk, t);
+                    if (ori != 2 && !key_eq<W>(t, tk)) {
+                        const uint64_t ds = graph_probe_slot<W>(g.tv, t);
+                        if (ds != NO_SLOT) {
+                            const int facing = (ori == 0) == (side == 0) ? 1 : 0;
+                            if (__popc(((uint32_t)g.u.edges[ds] >> (4 * facing)) & 15) == 1) {
+                                const uint32_t pid = g.u.id_of_slot[ds];
+                                if (pid < n_nodes && pid != id) nx = 2 * pid + (uint32_t)(1 - facing);
+                            }
+                        }
+                    }
+                }
+                const uint32_t x = 2 * id + (uint32_t)side;
+                g.u.succ[x] = nx;
+                UnitigState st;
+                st.mn = id;
+                st.stamp = 0;
+                if (nx == UNITIG_END) {
+                    st.nxt = x | UNITIG_DONE;
+                    st.dist = 0;
+                    st.sum = 0;
+                    g.u.st[1][x] = st;  // an end is final from the start: both buffers hold it
+                } else {
+                    st.nxt = nx;
+                    st.dist = 1;
+                    st.sum = g.u.tc[nx >> 1];
+                }
+                g.u.st[0][x] = st;
+            }
+        },
+        [] {});
+}
+
+template <int W>
+__global__ __launch_bounds__(GRAPH_T) void k_unitig_emit(TableView tv, int k, UnitigBufs u, uint8_t* __restrict__ bases) {
+    constexpr int S = BUCKET_WORDS / (W + 1);
+    const RollConst rk = make_roll<W>(k, 0, 0);
+    const uint64_t n_nodes = unitig_nodes(u), n_slots = tv.nbuckets * S;
+    for (uint64_t i = (uint64_t)blockIdx.x * GRAPH_T + threadIdx.x; i < n_nodes; i += (uint64_t)gridDim.x * GRAPH_T) {
+        const uint32_t st = u.start[i];
+        if (st >= n_nodes) continue;
+        const uint64_t off = u.off[2 * (uint64_t)st];
+        if (off == UNITIG_NO_OFF) continue;
+        const uint64_t slot = u.slot_of[i];
+        if (slot >= n_slots) continue;
+        const uint32_t p = u.pos[i], pos = p & 0x7FFFFFFFu;
+        if (pos >= u.off[2 * (uint64_t)st + 1]) continue;  // (past the length the offset was bounded with)
+        const uint64_t bucket = slot / S;
+        const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS + (slot - bucket * S) * W;
+        uint64_t tk[W], K[W], X[W];
+#pragma unroll
+        for (int j = 0; j < W; j++) tk[j] = bk[j];
+        from_tkey<W>(tk, K);
+        if (p >> 31) {
+            revcomp<W>(K, rk, X);
+        } else {
+#pragma unroll
+            for (int j = 0; j < W; j++) X[j] = K[j];
+        }
+        uint8_t* out = bases + off;
+        if (pos) {
+            out[(uint64_t)k - 1 + pos] = unitig_base(X[W - 1]);
+            continue;
+        }
+        // character j of the k-mer: bits 2 (k - 1 - j) and up of the 64 W-bit key
+#pragma unroll
+        for (int wi = 0; wi < W; wi++) {
+            const uint64_t w = X[wi];
+            const int j0 = k - 1 - 32 * (W - 1 - wi);  // the character in the word's lowest two bits
+#pragma unroll 1
+            for (int t = 0; t < 32; t++)
+                if (j0 - t >= 0) out[j0 - t] = unitig_base(w >> (2 * t));
+        }
+    }
+}
+
+template <int W>
+hipError_t UnitigOps<W>::succ(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, UnitigBufs u, hipStream_t s) {
+    if (!t.nbuckets) return hipSuccess;
+    const GraphArgs ga{t, k, count_mode, lo, hi, u.edges, nullptr, 0, nullptr};
+    const UnitigArgs g{t, k, count_mode, lo, hi, u};
+    const uint64_t items = GRAPH_BUCKET_MAP ? t.nbuckets : t.nbuckets * (uint64_t)(BUCKET_WORDS / (W + 1));
+    constexpr uint64_t TILE = graph_tile_items<W, GRAPH_BUCKET_MAP>();
+    const uint64_t need = (items + TILE - 1) / TILE;
+    const unsigned grid = (unsigned)(need < GRAPH_BLOCKS ? need : GRAPH_BLOCKS);
+    hipLaunchKernelGGL(k_graph_edges<W>, dim3(grid), dim3(GRAPH_T), 0, s, ga);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_unitig_number<W>, dim3(grid), dim3(GRAPH_T), 0, s, g);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_unitig_succ<W>, dim3(grid), dim3(GRAPH_T), 0, s, g);
+    return hipGetLastError();
+}
+
+template <int W>
+hipError_t UnitigOps<W>::emit(TableView t, int k, UnitigBufs u, uint8_t* bases, hipStream_t s) {
+    if (!t.nbuckets || !bases) return hipSuccess;
+    const uint64_t need = (u.bound + GRAPH_T - 1) / GRAPH_T;
+    const unsigned grid = (unsigned)(need < GRAPH_BLOCKS ? (need ? need : 1) : GRAPH_BLOCKS);
+    hipLaunchKernelGGL(k_unitig_emit<W>, dim3(grid), dim3(GRAPH_T), 0, s, t, k, u, bases);
+    return hipGetLastError();
+}
+
+}  // namespace kc

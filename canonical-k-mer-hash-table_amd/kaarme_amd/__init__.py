@@ -63,15 +63,23 @@ EXPORTS = (
     "kc_table_op_device", "kc_table_op",
     "kc_correct_device", "kc_correct",
     "kc_neighbors_device", "kc_neighbors", "kc_graph_device", "kc_graph",
+    "kc_unitigs_device", "kc_unitigs",
 )
 # kc_graph* node flags (KC_GRAPH_*): bits 0-7 the edges -- bit y: canon(c[1:] + y) is a node (side
 # R), bit 4 + y: canon(y + c[:-1]) is a node (side L) -- then the two unitig links and the node bit
 GRAPH_LINK_R, GRAPH_LINK_L, GRAPH_NODE = 0x0100, 0x0200, 0x8000
+UNITIG_CIRCULAR = 1  # kc_unitig.flags (KC_UNITIG_CIRCULAR)
 # kc_table_op* operations (KC_OP_*): on the raw counts ca, cb of a key in a and in b
 OP_INTERSECT_MIN, OP_INTERSECT_SUM, OP_INTERSECT_LEFT, OP_SUBTRACT, OP_COUNTS_SUBTRACT, OP_UNION_SUM, OP_UNION_MAX = range(7)
 OP_NAMES = {"intersect-min": OP_INTERSECT_MIN, "intersect-sum": OP_INTERSECT_SUM, "intersect-left": OP_INTERSECT_LEFT,
             "subtract": OP_SUBTRACT, "counts-subtract": OP_COUNTS_SUBTRACT, "union-sum": OP_UNION_SUM,
             "union-max": OP_UNION_MAX}
+
+
+def unitig_strings(records, bases, k: int) -> List[str]:
+    """the strings of unitig records (n, 4) {offset, n_nodes, ...}: bases[offset : offset + n_nodes + k - 1]"""
+    b = np.ascontiguousarray(bases, dtype=np.uint8).tobytes()
+    return [b[int(o):int(o) + int(n) + k - 1].decode("ascii") for o, n in np.asarray(records)[:, :2].tolist()]
 
 
 class KcError(RuntimeError):
@@ -133,6 +141,20 @@ class kc_graph_stats(ctypes.Structure):  # 80 bytes
         d["side_degree"] = [int(x) for x in self.side_degree]
         d["open_unitigs"] = d["nodes"] - d["link_ends"] // 2
         return d
+
+
+class kc_unitig(ctypes.Structure):  # 32 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("offset", "n_nodes", "count_sum", "flags")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_unitig_stats(ctypes.Structure):  # 40 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("unitigs", "circular", "nodes", "bases", "max_nodes")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class kc_correct_stat(ctypes.Structure):  # 16 bytes
@@ -248,6 +270,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_graph_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, P, P]),
         "kc_graph": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(U64)),
                            ctypes.POINTER(U64), ctypes.POINTER(kc_graph_stats)]),
+        "kc_unitigs_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, P]),
+        "kc_unitigs": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
+                             ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(kc_unitig_stats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -822,6 +847,44 @@ class KmerCounter:
         palindromes, side_degree[0..4] and open_unitigs (the non-circular unitigs)."""
         st = kc_graph_stats()
         self._chk(self.lib.kc_graph(self._ctx, min_count, max_count, None, None, ctypes.byref(st)), "kc_graph")
+        return st.as_dict()
+
+    # -- the unitigs of that graph (kc_unitigs*)
+    def unitigs_device(self, min_count: int = 1, max_count: int = 0, unitigs_ptr: int = 0, cap_unitigs: int = 0,
+                       bases_ptr: int = 0, cap_bases: int = 0, stats_ptr: int = 0, stream: int = 0):
+        """The unitigs of the graph whose nodes are the k-mers with min_count <= T(c) <= max_count,
+        all in device memory: a 32-byte kc_unitig {offset, n_nodes, count_sum, flags} per unitig at
+        unitigs_ptr (record i only when i < cap_unitigs), its n_nodes + k - 1 ASCII bases at
+        bases_ptr + offset (only when they end at or before cap_bases) and the 40-byte
+        kc_unitig_stats, always the full totals, at stats_ptr; each pointer may be 0.  Enqueued on
+        `stream`, no wait."""
+        self._chk(self.lib.kc_unitigs_device(self._ctx, min_count, max_count, ctypes.c_void_p(unitigs_ptr or None),
+                                             cap_unitigs, ctypes.c_void_p(bases_ptr or None), cap_bases,
+                                             ctypes.c_void_p(stats_ptr or None), ctypes.c_void_p(stream or None)),
+                  "kc_unitigs_device")
+
+    def unitigs(self, min_count: int = 1, max_count: int = 0) -> Tuple[np.ndarray, np.ndarray, dict]:
+        """(records, bases, statistics): records (n, 4) uint64 {offset, n_nodes, count_sum, flags} in
+        an unspecified order, bases a uint8 array of ASCII ACGT that holds unitig i's n_nodes + k - 1
+        bases from records[i, 0] on (unitig_strings cuts them out), the statistics as
+        unitig_stats()."""
+        pr, pb, st = ctypes.POINTER(kc_unitig)(), ctypes.POINTER(ctypes.c_uint8)(), kc_unitig_stats()
+        self._chk(self.lib.kc_unitigs(self._ctx, min_count, max_count, ctypes.byref(pr), ctypes.byref(pb),
+                                      ctypes.byref(st)), "kc_unitigs")
+        try:
+            recs = (np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint64)), shape=(st.unitigs * 4,)).copy()
+                    if st.unitigs else np.zeros(0, dtype=np.uint64))
+            bases = np.ctypeslib.as_array(pb, shape=(st.bases,)).copy() if st.bases else np.zeros(0, dtype=np.uint8)
+        finally:
+            self.lib.kc_free(pr)
+            self.lib.kc_free(pb)
+        return recs.reshape(-1, 4), bases, st.as_dict()
+
+    def unitig_stats(self, min_count: int = 1, max_count: int = 0) -> dict:
+        """The unitigs' totals without records or bases: unitigs, circular, nodes, bases (= nodes +
+        (k - 1) * unitigs) and max_nodes (the longest unitig)."""
+        st = kc_unitig_stats()
+        self._chk(self.lib.kc_unitigs(self._ctx, min_count, max_count, None, None, ctypes.byref(st)), "kc_unitigs")
         return st.as_dict()
 
     def compact_read(self, info: dict):

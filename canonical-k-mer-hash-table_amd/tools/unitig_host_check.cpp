@@ -1,0 +1,69 @@
+// unitig_host_check.cpp -- the host arithmetic of the unitig layer (csrc/kc_unitig_host.h) in a
+// program of its own, for the sanitizers:
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o bin/unitig_host_check tools/unitig_host_check.cpp
+// (make bin/unitig_host_check).  It touches no device and exits 0 when every check holds.
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../csrc/kc_unitig_host.h"
+
+#define CHECK(x)                                                          \
+    do {                                                                  \
+        if (!(x)) {                                                       \
+            std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #x);  \
+            return 1;                                                     \
+        }                                                                 \
+    } while (0)
+
+int main() {
+    using namespace kc;
+    // rounds: ceil(log2(2 * bound)) + 1
+    CHECK(unitig_rounds(0) == 2 && unitig_rounds(1) == 2 && unitig_rounds(2) == 3 && unitig_rounds(3) == 4);
+    CHECK(unitig_rounds(19970) == 17);  // 2^15 < 39940 <= 2^16; the chain itself needs 15 of them
+    CHECK(unitig_rounds(UNITIG_MAX_BOUND - 1) == 32 && unitig_rounds(UNITIG_MAX_BOUND) == 32);
+    CHECK(unitig_rounds(~0ULL) == 64);  // (saturates instead of shifting past the word)
+    for (uint64_t b = 1; b < 5000; b++) {
+        const int r = unitig_rounds(b);
+        CHECK((1ULL << (r - 1)) >= 2 * b && (r == 2 || (1ULL << (r - 2)) < 2 * b));
+    }
+    // scratch
+    CHECK(unitig_scratch_bytes(0, 0) == 0 && unitig_scratch_bytes(1 << 20, 1000) == 5ULL * (1 << 20) + 140 * 1000);
+    CHECK(unitig_scratch_bytes(268435456ULL, 86000000ULL) == 5 * 268435456ULL + 140 * 86000000ULL);
+    CHECK(unitig_scratch_bytes(~0ULL, 1) == 0 && unitig_scratch_bytes(1, ~0ULL) == 0);
+    CHECK(unitig_scratch_bytes(~0ULL / 5, ~0ULL / 140) == 0);
+    // the layout: disjoint arrays, in order, inside `words`, and within the bytes the header states
+    for (uint64_t b : std::vector<uint64_t>{1, 2, 3, 1000, 86000001, UNITIG_MAX_BOUND - 1}) {
+        const UnitigLayout l = unitig_layout(b);
+        const uint64_t half = (b + 1) / 2;
+        CHECK(l.st0 == 0 && l.st1 - l.st0 == 6 * b && l.slot_of - l.st1 == 6 * b && l.off - l.slot_of == b);
+        CHECK(l.succ - l.off == 2 * b && l.tc - l.succ == b && l.start - l.tc == half && l.pos - l.start == half);
+        CHECK(l.words - l.pos == half && l.words * 8 <= UNITIG_NODE_BYTES * b + 24);
+    }
+    {  // every word of a small layout belongs to exactly one array
+        const uint64_t b = 7;
+        const UnitigLayout l = unitig_layout(b);
+        std::vector<int> owner(l.words, 0);
+        const uint64_t at[] = {l.st0, l.st1, l.slot_of, l.off, l.succ, l.tc, l.start, l.pos};
+        const uint64_t len[] = {6 * b, 6 * b, b, 2 * b, b, 4, 4, 4};
+        for (int a = 0; a < 8; a++)
+            for (uint64_t w = 0; w < len[a]; w++) owner[at[a] + w]++;
+        for (int o : owner) CHECK(o == 1);
+    }
+    // the FASTA header
+    char buf[160];
+    int n = unitig_fasta_header(buf, sizeof buf, 0, 3, 10, 31, false);
+    CHECK(n == (int)std::strlen(buf) && std::string(buf) == ">0 LN:i:33 KC:i:10 km:f:3.3");
+    unitig_fasta_header(buf, sizeof buf, 17, 2, 50, 31, true);
+    CHECK(std::string(buf) == ">17 LN:i:32 KC:i:50 km:f:25.0 circular");
+    n = unitig_fasta_header(buf, sizeof buf, ~0ULL, ~0ULL - 600, ~0ULL, 479, true);  // the longest it gets
+    CHECK(n > 0 && n < (int)sizeof buf && n == (int)std::strlen(buf));
+    char tiny[8];
+    n = unitig_fasta_header(tiny, sizeof tiny, 123456, 5, 5, 31, false);  // truncated, never past the buffer
+    CHECK(n > (int)sizeof tiny && std::strlen(tiny) == sizeof tiny - 1);
+    unitig_fasta_header(buf, sizeof buf, 1, 0, 0, 0, false);  // no division by zero
+    CHECK(std::string(buf) == ">1 LN:i:0 KC:i:0 km:f:0.0");
+    std::puts("unitig_host_check: OK");
+    return 0;
+}

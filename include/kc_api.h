@@ -569,6 +569,70 @@ int kc_graph_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, uint64_
 int kc_graph(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, uint64_t** records, uint64_t* n_records,
              kc_graph_stats* stats);
 
+/* The unitigs of that graph: the sequences the link bits spell.  Compacted unitigs are what
+ * assemblers, variant callers and colored-graph indexers read, what BCALM and GGCAT write, and the
+ * compact lossless form of the k-mer set: nodes + (k - 1) * unitigs bases instead of k * nodes.  All
+ * terms are kc_graph_device's: node, range, side, facing side, link(c, s).
+ *   unitig        a maximal path of links c_0 ... c_{n-1}, each node read on one strand, x_i in
+ *                 {c_i, rc(c_i)} with x_{i+1}[:-1] == x_i[1:]; its string is x_0 followed by the last
+ *                 character of each later x_i, n + k - 1 bases over ACGT.  Every node lies in exactly
+ *                 one unitig; a node without links is a unitig of one node.
+ *   strand        unspecified: either of the two strings of a unitig is a right answer (a one-node
+ *                 unitig may be c or rc(c)).
+ *   circular      the link at the far side of c_{n-1} leads back to c_0 (then n >= 2).  It is
+ *                 written as the same n + k - 1 bases starting at an unspecified node, so its last
+ *                 k - 1 bases repeat its first k - 1, and it is flagged KC_UNITIG_CIRCULAR.
+ *   states        the method rests on the directed states (node, exit side): next(c, s) = (d, the
+ *                 other side of d's facing side) when link(c, s) holds, nothing otherwise.  next is
+ *                 injective and rev(c, s) = (c, 1 - s) reverses it; self-links are excluded by the
+ *                 link rule, so the states form disjoint paths and cycles, each unitig is two paths
+ *                 or two cycles that mirror each other, and no path passes one node twice.  Paths
+ *                 are ranked by pointer jumping in ceil(log2(longest path)) rounds; nothing walks a
+ *                 unitig node by node.
+ *   kc_unitigs_device  one kc_unitig per unitig and its bases (ASCII ACGT, one byte each) at
+ *                 dev_bases + offset.  Record order and offset order are unspecified, as kc_graph's
+ *                 record order is.  The offsets are distinct, non-overlapping places in [0,
+ *                 stats.bases), handed out whatever the capacities are; record i is written only
+ *                 when i < cap_unitigs, a unitig's bases only when offset + n_nodes + k - 1 <=
+ *                 cap_bases, and nothing is written past either capacity.  *dev_stats always holds
+ *                 the full totals, so a statistics-only call sizes a second one.  dev_unitigs,
+ *                 dev_bases and dev_stats (device memory) may each be NULL.
+ *   kc_unitigs    the same in host memory of the exact size (free both with kc_free); any of the
+ *                 three out-pointers may be NULL; waits.  The ranking runs once: rank, read the
+ *                 totals, allocate, write.
+ * kc_unitigs_device follows the *_device rule as kc_graph_device does: staged host chunks are
+ * flushed first, the work runs on hip_stream after what is queued there and after the context's own
+ * stream, and the context's later work follows it; no host wait -- the number of jump launches is
+ * fixed by the host, ceil(log2(2 * ids)) + 1 for each of the two rankings (the second ranks the
+ * circles, cut at their least node), and a launch whose predecessor moved no state returns at once.
+ * Errors are kc_graph's: KC_ERR_ARG for k < 2 or min_count above a non-zero max_count, KC_ERR_STATE
+ * without a table or after a failed pass, KC_ERR_NOMEM when the scratch does not fit -- reported
+ * before any kernel of kc_unitigs_device is launched; kc_unitigs first runs and waits for the
+ * count-only sweep that sizes the scratch, and reports it before any kernel of the ranking; an
+ * emptied table gives zero unitigs.  The table is only read and
+ * no counter of kc_stats changes.
+ * Scratch of the context (grows only, shared with kc_graph's edge bytes): 5 bytes per table slot
+ * (kc_stats.table_slots: the edge byte, the slot's node id) and 140 bytes per node id -- two states
+ * of 24 bytes in each of two buffers, two successors, T(c), the slot, and the unitig's start,
+ * position, offset and length.  kc_unitigs counts the k-mers with T(c) >= min_count first and has
+ * that many ids (>= the nodes); kc_unitigs_device cannot wait for a count and has table_slots ids:
+ *   scratch = 5 * table_slots + 140 * ids bytes,  ids < 2^30 (else KC_ERR_NOMEM).
+ * The kernels work on the nodes there are, whatever the ids allocated. */
+#define KC_UNITIG_CIRCULAR 1u  /* kc_unitig.flags: the unitig is circular */
+typedef struct {            /* 32 bytes */
+    uint64_t offset;        /* of its first base, counted in an unbounded bases buffer */
+    uint64_t n_nodes;       /* its string has n_nodes + k - 1 bases */
+    uint64_t count_sum;     /* sum of T(c) over its nodes (mean abundance = count_sum / n_nodes) */
+    uint64_t flags;         /* KC_UNITIG_CIRCULAR 1; every other bit 0 */
+} kc_unitig;
+typedef struct {            /* 40 bytes */
+    uint64_t unitigs, circular, nodes, bases, max_nodes;   /* bases = nodes + (k-1)*unitigs; max_nodes = longest unitig */
+} kc_unitig_stats;
+int kc_unitigs_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig* dev_unitigs, uint64_t cap_unitigs,
+                      uint8_t* dev_bases, uint64_t cap_bases, kc_unitig_stats* dev_stats, void* hip_stream);
+int kc_unitigs(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+               kc_unitig_stats* stats);   /* kc_free both */
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
