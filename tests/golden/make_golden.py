@@ -103,6 +103,11 @@ CASES = [
     ("long_lo.fasta", 479, ["-a", "2", "-s", "1000000"]),
     ("long_lo.fasta", 479, ["-m", "0", "-a", "3", "-s", "1000000"]),
     ("long_lo.fasta", 479, ["-m", "0", "-b", "-u", "300000", "-a", "1"]),
+    # eleven- and thirteen-word keys (k = 320..351, 384..415)
+    ("long_lo.fasta", 351, ["-a", "1", "-s", "1000000"]),
+    ("long_lo.fasta", 415, ["-a", "1", "-s", "1000000"]),
+    ("long_lo.fasta", 351, ["-b", "-u", "300000", "-a", "2"]),
+    ("long_lo.fasta", 415, ["-b", "-u", "300000", "-a", "2"]),
     ("big_edge.fasta", 161, ["-a", "1", "-s", "8000000"]),
     # skew (hot keys: homopolymers, dinucleotide repeats, a high-copy repeat)
     ("skew.fasta", 31, ["-a", "1", "-s", "4000000"]),
