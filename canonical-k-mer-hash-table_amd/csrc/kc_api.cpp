@@ -203,55 +203,20 @@ int materialize_zero(kc_ctx* c, hipStream_t s) {
 // 8 standard deviations plus 32, from the batch's symbol bound (>= its windows).  A
 // batch whose keys still overflow a segment (e.g. one k-mer repeated millions of times
 // inside one workgroup's range) is redone on the exact layout by the device itself.
+// The arithmetic is plan_partition (kc_plan_host.h); the tests' knobs are read here.
 PartPlan part_plan(const kc_ctx* c, uint64_t syms, bool seg, const PartGeo& g, uint32_t bins1, uint32_t slots,
                    uint64_t rec2, bool tight) {
-    PartPlan p{};
-    const uint64_t tile = (uint64_t)COUNT_THREADS * run_width(c->W);
-    p.nblk1 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (syms + tile - 1) / tile));
-    p.B2 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, 2048 / g.F1));
-    // every array is sized for the geometry of THIS call (a Bloom job re-sizes the table
-    // after each Bloom pass, so F1 and R may grow between calls on one context)
-    p.n1 = (uint64_t)std::max<uint32_t>(g.F1, bins1) * 2048;  // level-1 bins x max workgroups
-    p.n2 = g.R * p.B2 * slots;
-    p.nbs = (std::max(p.n1, p.n2) + 4095) / 4096 + 2;
-    if (seg) {
-        // tight (a deferred pass): e + 3.5 sigma + 8.  Its keys past a segment's end (a few segments
-        // in 10^4 overflow, by a few keys) join the group's skew list, which is inserted once after
-        // the group's level 3 (run_deferred), so the slots of more batches fit beside the table (C5
-        // on one GPU: 54.2 -> 43.4 GB per batch, groups of 2 -> 3).  (At 3 sigma, C5's ~54 K spilled
-        // keys per batch touched ~100 K regions per group in the list's level 3: 12 ms per job.)
-        const double sd = tight ? 3.5 : 8.0, add = tight ? 8.0 : 32.0;
-        auto capacity = [&](double e) { return ((uint64_t)std::ceil(e + sd * std::sqrt(e) + add) + 7) / 8 * 8; };
-        const uint64_t t1 = (uint64_t)p1_tile_max(c->W);  // k_p1<..., OutSeg> rounds block ranges to its tile
-        const uint64_t per1 = ((syms + p.nblk1 - 1) / p.nblk1 + t1 - 1) / t1 * t1;  // symbols per level-1 block
-        const uint64_t nseg = (p.nblk1 + p.B2 - 1) / p.B2;                           // level-1 segments per p2 block
-        const double d = c->win_density;  // windows per symbol (1 for tokenized input)
-        p.cap1 = capacity((double)per1 * d / g.F1);
-        p.cap2 = capacity((double)nseg * per1 * d / g.F1 / g.F2);
-        if (const char* v = std::getenv("KC_SEG_CAP")) p.cap1 = p.cap2 = std::max<uint64_t>(1, std::strtoull(v, 0, 10));
-        // the segment walks index a virtual run with 32-bit offsets
-        if (nseg * p.cap1 >= (1ULL << 31) || (uint64_t)p.B2 * p.cap2 * slots >= (1ULL << 31)) p.cap1 = p.cap2 = 0;
+    PlanKnobs kn;
+    if (const char* v = std::getenv("KC_SEG_CAP")) {
+        kn.has_seg_cap = true;
+        kn.seg_cap = std::strtoull(v, 0, 10);
     }
-    // the skew list of a segmented batch: {key words, count} records of keys past a segment's
-    // end and of repeated windows (Bloom pass: plain keys), an eighth of the windows before the
-    // batch falls back to the exact layout; its exact pipeline runs through the key buffers
-    const uint64_t wins = c->win_density < 1.0 ? (uint64_t)((double)syms * c->win_density) + 1024 : syms;
-    if (p.cap1) {
-        // (a deferred pass's list takes its group's few spilled keys: a sixteenth)
-        p.spill_cap = std::max<uint64_t>(1 << 16, wins / (tight ? 16 : 8));
-        if (const char* v = std::getenv("KC_SPILL_CAP")) p.spill_cap = std::strtoull(v, 0, 10);  // tests
+    if (const char* v = std::getenv("KC_SPILL_CAP")) {
+        kn.has_spill_cap = true;
+        kn.spill_cap = std::strtoull(v, 0, 10);
     }
-    p.spill_words = p.spill_cap * (g.IW + 1);
-    p.need1 = std::max(std::max<uint64_t>(wins, (uint64_t)g.F1 * p.nblk1 * p.cap1) * g.IW, p.spill_words);
-    // one batch's level 2 in W-word items; a deferred group's slots in level-2 records (the exact
-    // pipeline of a batch's tail, which writes W-word items, runs after its group's level 3)
-    const uint64_t l2 = slots > 1 && rec2 ? (g.R * p.B2 * p.cap2 * slots * rec2 + 7) / 8 : g.R * p.B2 * p.cap2 * g.IW;
-    p.need2 = std::max(std::max<uint64_t>(wins * g.IW, l2), p.spill_words);
-    // (the levels' record loads are 12 or 16 bytes wide whatever the record: a last 8- or
-    // 12-byte record's load reads past it)
-    p.need1 += 2;
-    p.need2 += 2;
-    return p;
+    // c->win_density: windows per symbol of the batches being planned (1 for tokenized input)
+    return plan_partition(c->W, syms, c->win_density, seg, g, bins1, slots, rec2, tight, kn);
 }
 
 // Partition buffers for a batch of up to `syms` symbols (lazily grown): part_plan's sizes

@@ -827,7 +827,11 @@ int kc_estimate_distinct_device(kc_ctx* c, const uint8_t* img, const kc_chunk* c
 
 // A symbol stream in HBM (a received super-k-mer stream) through the pass's levels in batches of
 // about a staging batch's windows, cut at words whose first symbol is a break (no window spans a
-// cut), with the deferred level 3 of a counting pass over several batches.
+// cut), with the deferred level 3 of a counting pass over several batches.  `windows` is the
+// caller's hint and only chooses the cut length (packed_cut_words); the buffers are sized from the
+// windows counted in each batch (k_packed_windows: one read of the batches' break words and one
+// host wait per pass), since the exact pipeline writes every window of a batch unchecked and a
+// stream need not be uniform (kc_plan_host.h packed_batch_density).
 static int packed_pass(kc_ctx* c, const uint64_t* pk, const uint32_t* bk, uint64_t n_words, uint64_t windows, int pass,
                        hipStream_t s) {
     int rc = flush_host(c);  // keep order with staged host chunks
@@ -838,9 +842,7 @@ static int packed_pass(kc_ctx* c, const uint64_t* pk, const uint32_t* bk, uint64
         on.no_hand_back();  // (nothing ran on s)
         return KC_OK;
     }
-    const double nsym = (double)n_words * 32.0;
-    const double dens = windows ? std::min(1.0, 1.15 * (double)windows / nsym + 1e-3) : 1.0;
-    const uint64_t lim = std::max<uint64_t>(1024, (uint64_t)((double)c->batch_bytes / dens) / 32);
+    const uint64_t lim = packed_cut_words(c->batch_bytes, n_words, windows);
     std::vector<uint64_t> cuts{0};
     std::vector<uint32_t> probe(4096);
     while (n_words - cuts.back() > lim) {
@@ -862,6 +864,18 @@ static int packed_pass(kc_ctx* c, const uint64_t* pk, const uint32_t* bk, uint64
     const uint64_t nb = cuts.size() - 1;
     uint64_t maxs = 0;
     for (uint64_t i = 0; i < nb; i++) maxs = std::max<uint64_t>(maxs, (cuts[i + 1] - cuts[i]) * 32);
+    // every batch's windows, counted; the pass plans at the largest windows per symbol of a batch
+    std::vector<unsigned long long> bw(nb);
+    if (!c->d_pwin.reserve(nb)) return c->fail(KC_ERR_NOMEM, "window count allocation failed");
+    HIPCHK(c, hipMemsetAsync(c->d_pwin, 0, nb * 8, s));
+    for (uint64_t i = 0; i < nb; i++)
+        HIPCHK(c, launch_packed_windows(bk + cuts[i], cuts[i + 1] - cuts[i], c->cfg.k, c->d_pwin + i, s));
+    HIPCHK(c, hipMemcpyAsync(bw.data(), c->d_pwin, nb * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    double measured = 0;
+    for (uint64_t i = 0; i < nb; i++)
+        measured = std::max(measured, packed_batch_density(bw[i], (cuts[i + 1] - cuts[i]) * 32));
+    const double dens = packed_plan_density(packed_hint_density(n_words, windows), measured);
     struct Density {
         kc_ctx* c;
         double d;
@@ -890,6 +904,23 @@ int kc_count_packed_device(kc_ctx* c, const uint64_t* pk, const uint32_t* bk, ui
     if (!c->nbuckets) return c->fail(KC_ERR_STATE, "kc_bloom_finalize must precede the counting pass");
     c->reuse_ok = false;  // (the Bloom pass's kept partitions are an image's)
     return packed_pass(c, pk, bk, n_words, windows, 0, (hipStream_t)sp);
+}
+
+int kc_packed_windows_device(kc_ctx* c, const uint64_t* pk, const uint32_t* bk, uint64_t n_words, void* sp,
+                             uint64_t* windows) {
+    (void)pk;  // (the windows of a stream depend on its breaks alone)
+    if (!c || !windows || (n_words && !bk)) return KC_ERR_ARG;
+    *windows = 0;
+    if (n_words == 0) return KC_OK;
+    hipStream_t s = (hipStream_t)sp;
+    if (!c->d_pwin.reserve(1)) return c->fail(KC_ERR_NOMEM, "window count allocation failed");
+    unsigned long long n = 0;
+    HIPCHK(c, hipMemsetAsync(c->d_pwin, 0, 8, s));
+    HIPCHK(c, launch_packed_windows(bk, n_words, c->cfg.k, c->d_pwin, s));
+    HIPCHK(c, hipMemcpyAsync(&n, c->d_pwin, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    *windows = n;
+    return KC_OK;
 }
 
 int kc_bloom_packed_device(kc_ctx* c, const uint64_t* pk, const uint32_t* bk, uint64_t n_words, uint64_t windows,

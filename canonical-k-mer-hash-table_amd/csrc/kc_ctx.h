@@ -270,6 +270,7 @@ struct kc_ctx {
     // super-k-mer routing (kc_route_superkmers_device): the pass-4 batches' parameters and the
     // device cursors [0, 64) words per owner, [64, 128) windows per owner, [128] overflow flag
     DevBuf<unsigned long long> d_skm;
+    DevBuf<unsigned long long> d_pwin;  // a packed pass's counted windows per batch (k_packed_windows)
     uint32_t skm_shards = 0;
     int skm_m = 0;
     uint64_t* skm_pk = nullptr;  // borrowed: the caller's output streams, for the length of
@@ -423,24 +424,8 @@ struct StreamScope {
 // ---- helpers shared by the kc_api*.cpp files (defined in the file named) -------------------------
 inline uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
-// geometry of a partitioned pass: F1 coarse bins x F2 regions each (R regions), IW
-// u64 words per item
-struct PartGeo {
-    uint32_t F1, F2;
-    uint64_t R;
-    int IW;
-};
+// (PartGeo, PartPlan: kc_plan_host.h)
 inline PartGeo table_geo(const kc_ctx* c) { return PartGeo{c->F1, c->F2, c->R, c->W}; }
-// The sizes of a partitioned pass over a batch of up to `syms` symbols (no allocation):
-// level-1 workgroups, level-2 segments per bin, the segment capacities, the skew list and the key
-// buffers' words.  slots > 1: the level-2 histogram and key buffers hold that many batches'
-// segments (a deferred level 3, run_deferred), each record rec2 bytes (level2_record_bytes)
-struct PartPlan {
-    uint32_t nblk1, B2;
-    uint64_t n1, n2, nbs;     // histogram entries: level 1, level 2, block sums
-    uint64_t cap1, cap2;      // segment capacities (0: the exact layout)
-    uint64_t spill_cap, spill_words, need1, need2;
-};
 
 // kc_api.cpp
 uint64_t bloom_blocks(uint64_t bits);

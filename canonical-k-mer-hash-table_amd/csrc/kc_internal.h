@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/kc_api.h"
+#include "kc_plan_host.h"  // run_width, p1_tile, p1_tile_max, COUNT_THREADS: shared with the host's sizing
 
 namespace kc {
 
@@ -14,7 +15,6 @@ namespace kc {
 // chunks; the tokenizer then works per 4 KiB tile.
 constexpr int TILE = 4096;
 constexpr int TILE_THREADS = 256;          // 16 bytes per thread
-constexpr int COUNT_THREADS = 256;
 constexpr int RUN = 32;                    // consecutive symbols rolled per thread
 constexpr int BUCKET_WORDS = 16;           // 128-byte buckets
 constexpr int BPR = 512;                   // buckets per region: 64 KiB, one LDS-resident table (2^BPR_BITS)
@@ -185,16 +185,7 @@ constexpr int MAX_W = 15;      // (KCO_MAXW of the oracle)
 inline int words_for_k(int k) { return k / 32 + 1; }          // spare top bit for EMPTY
 inline int slots_per_bucket(int W) { return BUCKET_WORDS / (W + 1); }
 
-// Windows rolled per thread in the partitioned kernels, and the workgroup size of the
-// segmented level 1 (tile = threads x windows), by key width: wide keys take fewer
-// windows per thread and smaller groups so that the registers and the LDS tile fit.
-constexpr int run_width(int W) { return W == 1 ? 16 : W == 2 ? 8 : W <= 4 ? 8 : 4; }
-// The segmented level 1 (k_p1) of one- to four-word keys: 512-thread workgroups, two per CU.
-// (1024 threads with half the windows per thread -- 8 waves per SIMD within 64 VGPRs -- spill
-// and ran 30 % slower: profiles/r03_ab_p1_nt.txt)
-constexpr int scatter_threads_w(int W) { return W <= 4 ? 512 : 256; }
-constexpr int p1_runw(int W) { return run_width(W); }
-constexpr int p1_tile(int W) { return scatter_threads_w(W) * p1_runw(W); }  // windows per segmented level-1 tile
+// (run_width, scatter_threads_w, p1_runw, p1_tile: kc_plan_host.h)
 // level 2 (k_p2f): workgroup size by key width, and its LDS for F2 regions per coarse bin
 // a scatter's per-bin LDS arrays (k_count_impl.h PartLds: 4 x u32 + 1 x u64 per bin, the
 // tile's keys after them at a 16-byte boundary) and its static extras
@@ -217,7 +208,7 @@ constexpr size_t LDS_BYTES = 160 * 1024;  // per CU (one workgroup may take all 
 // workgroup per CU (8 waves) so that L2 merges the partial lines.  Two-word keys take a
 // 1024-thread level 1 instead (one workgroup per CU, 16 waves, 128 VGPRs): an 8192-window
 // tile, runs twice as long, when its LDS fits beside the bins.
-constexpr int P1_WIDE_THREADS = 1024;
+// (P1_WIDE_THREADS, p1_tile_max: kc_plan_host.h)
 constexpr size_t p1_lds_bytes_nt(int W, uint32_t F1, int nt) {
     return bin_lds_bytes(F1) + (size_t)nt * p1_runw(W) * 8 * W + (size_t)64 * (W + 1) * 8 +
            (size_t)(nt * p1_runw(W) / 32 + W + 3) * 24;
@@ -225,9 +216,6 @@ constexpr size_t p1_lds_bytes_nt(int W, uint32_t F1, int nt) {
 constexpr bool p1_wide(int W, uint32_t F1) {
     return W == 2 && (uint64_t)p1_tile(W) < 8ULL * F1 && p1_lds_bytes_nt(W, F1, P1_WIDE_THREADS) <= LDS_BYTES;
 }
-// the largest level-1 tile a table pass of W-word keys may run (the host's segment sizing rounds
-// block ranges to it)
-constexpr int p1_tile_max(int W) { return W == 2 ? P1_WIDE_THREADS * p1_runw(W) : p1_tile(W); }
 
 // ---- launchers (kc_tokenize.hip, kc_count.hip) -------------------------------------------------
 // src: bytes the chunk descriptors' src_off point into (host stage or device image)
@@ -316,6 +304,9 @@ constexpr uint32_t HLL_M = 1u << HLL_P;
 // strand-symmetric hash of the canonical key picks them): the estimate is 2^HLL_SB x the sample's
 constexpr int hll_sample_bits(int W) { return W <= 4 ? 3 : 0; }
 hipError_t launch_hll(PackedView sym, int k, int W, DevCounters* ctr, uint32_t* regs, hipStream_t s);
+// *out += the windows (break-free runs of k symbols) that end in the break words bk[0 .. n_words) of a
+// packed stream (kc_util.hip k_packed_windows; the caller zeroes *out)
+hipError_t launch_packed_windows(const uint32_t* bk, uint64_t n_words, int k, unsigned long long* out, hipStream_t s);
 // Super-k-mer routing of a tokenized batch to nshards owners by canonical minimizer (kc_skm.hip):
 // per owner a packed symbol stream (out_pk / out_bk regions of cap words), cursor[] = words used,
 // wins[] = windows routed, *ovf = 1 if a region overflowed

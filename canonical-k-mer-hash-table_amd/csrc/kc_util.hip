@@ -1,6 +1,7 @@
 // kc_util.hip -- small device helpers: the device XXH64 of the reference-layout Bloom
 // passes (kc_common.h xxh64_u64) over host-given inputs (test hook), the chunk checksum of
-// the partition reuse, the sharded Bloom filter's merge and filter-2 bit count, and the
+// the partition reuse, the sharded Bloom filter's merge and filter-2 bit count, the window
+// counter of a packed stream's break words (kc_packed_windows_device, packed_pass), and the
 // W-dispatch of the table queries (kc_query_w.hip), of the table algebra (kc_join_w.hip) and of
 // the de Bruijn graph kernels (kc_graph_w.hip).
 #include "kc_common.h"
@@ -151,6 +152,59 @@ __global__ void k_hold_overflow(DevCounters* ctr, int restore) {
 
 hipError_t launch_hold_overflow(DevCounters* ctr, int restore, hipStream_t s) {
     hipLaunchKernelGGL(k_hold_overflow, dim3(1), dim3(1), 0, s, ctr, restore);
+    return hipGetLastError();
+}
+
+// Windows of a range of a packed stream's break words (kc_packed_windows_device; packed_pass sizes
+// its batches' buffers from it): symbols that are no break and have k - 1 break-free predecessors
+// inside the range, i.e. the sum of max(0, L - k + 1) over its maximal break-free runs.  The symbol
+// before the range counts as a break (run_windows starts a stream the same way) and the range ends
+// with its last word (the levels' stream length is a whole number of words).  A thread takes PW_PER
+// words: the run that reaches a word is found by looking back at most ceil((k - 1) / 32) words, so
+// only the break words are read, each about once from HBM.  Host form: packed_windows_host.
+constexpr int PW_T = 256, PW_PER = 8;
+__global__ __launch_bounds__(PW_T) void k_packed_windows(const uint32_t* __restrict__ bk, uint64_t n_words, int k,
+                                                         unsigned long long* __restrict__ out) {
+    unsigned long long n = 0;
+    const uint64_t w0 = ((uint64_t)blockIdx.x * PW_T + threadIdx.x) * PW_PER;
+    if (w0 < n_words) {
+        int run = 0;  // break-free symbols that end just before word w0, capped at k - 1
+        for (uint64_t v = w0; v > 0 && run < k - 1; v--) {
+            const uint32_t m = bk[v - 1];
+            if (m) {
+                run += __builtin_ctz(m);  // (break j at bit 31 - j: the symbols after the word's last break)
+                break;
+            }
+            run += 32;
+        }
+        run = min(run, k - 1);
+        const uint64_t w1 = min(n_words, w0 + PW_PER);
+        for (uint64_t w = w0; w < w1; w++) {
+            const uint32_t m = bk[w];
+#pragma unroll
+            for (int j = 0; j < 32; j++) {
+                run = (m >> (31 - j)) & 1 ? 0 : min(run + 1, k);
+                n += run >= k;
+            }
+        }
+    }
+    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o, 64);
+    __shared__ unsigned long long s_n[PW_T / 64];
+    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < PW_T / 64; w++) t += s_n[w];
+        if (t) atomicAdd(out, t);
+    }
+}
+
+// *out += the windows of bk[0 .. n_words) (the caller zeroes it)
+hipError_t launch_packed_windows(const uint32_t* bk, uint64_t n_words, int k, unsigned long long* out, hipStream_t s) {
+    if (n_words == 0) return hipSuccess;
+    const uint64_t per = (uint64_t)PW_T * PW_PER;
+    hipLaunchKernelGGL(k_packed_windows, dim3((unsigned)((n_words + per - 1) / per)), dim3(PW_T), 0, s, bk, n_words, k,
+                       out);
     return hipGetLastError();
 }
 

@@ -58,6 +58,7 @@ EXPORTS = (
     "kc_bloom_estimate", "kc_compact", "kc_compact_dump", "kc_compact_lookup", "kc_compact_read", "kc_size_table",
     "kc_estimate_distinct_device", "kc_bloom_records_device", "kc_count_records_device", "kc_plan_chunks_device",
     "kc_output_digest", "kc_route_superkmers_device", "kc_count_packed_device", "kc_bloom_packed_device",
+    "kc_packed_windows_device",
     "kc_lookup_device", "kc_lookup", "kc_histogram",
     "kc_text_counts_device", "kc_text_counts", "kc_seq_stats_device", "kc_seq_stats",
     "kc_table_op_device", "kc_table_op",
@@ -210,6 +211,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                              I32, P, P, U64, ctypes.POINTER(U64), ctypes.POINTER(U64), P]),
         "kc_count_packed_device": (I32, [P, P, P, U64, U64, P]),
         "kc_bloom_packed_device": (I32, [P, P, P, U64, U64, P]),
+        "kc_packed_windows_device": (I32, [P, P, P, U64, P, ctypes.POINTER(ctypes.c_uint64)]),
         "kc_sync": (I32, [P]),
         "kc_finish": (I32, [P, ctypes.POINTER(kc_stats)]),
         "kc_dump": (I32, [P, ctypes.POINTER(ctypes.POINTER(U64)), ctypes.POINTER(U64)]),
@@ -526,6 +528,16 @@ class KmerCounter:
         self._chk(self.lib.kc_bloom_packed_device(self._ctx, ctypes.c_void_p(pk_ptr or None),
                                                   ctypes.c_void_p(bk_ptr or None), n_words, windows,
                                                   ctypes.c_void_p(stream or None)), "kc_bloom_packed_device")
+
+    def packed_windows_device(self, pk_ptr: int, bk_ptr: int, n_words: int, stream: int = 0) -> int:
+        """The windows of a packed symbol stream in HBM, counted from its break words: the honest
+        value of the `windows` hint of count_packed_device / bloom_packed_device."""
+        n = ctypes.c_uint64(0)
+        self._chk(self.lib.kc_packed_windows_device(self._ctx, ctypes.c_void_p(pk_ptr or None),
+                                                    ctypes.c_void_p(bk_ptr or None), n_words,
+                                                    ctypes.c_void_p(stream or None), ctypes.byref(n)),
+                  "kc_packed_windows_device")
+        return int(n.value)
 
     def route_device(self, dev_ptr: int, chunks, fmt: int, nshards: int, out_ptr: int, out_capacity: int,
                      stream: int = 0) -> List[int]:

@@ -486,7 +486,8 @@ class ShardedCounter:
 
                 torch.cuda.synchronize()
                 self.xstats["insert_s"] += time.perf_counter() - ti
-        self._inflight = [pk, bk]  # the receive buffers must outlive the count
+        # the receive buffers must outlive the count: kept (beside an earlier pass's) until sync()
+        self._inflight += [pk, bk]
 
     # the counting pass over a device image (chunks from kaarme_amd.plan_chunks): local
     def count_device(self, dev_ptr: int, chunks: List[Tuple[int, int, int]], fmt: int, stream: int = 0):
@@ -546,7 +547,7 @@ class ShardedCounter:
 
                 torch.cuda.synchronize()
                 self.xstats["insert_s"] += time.perf_counter() - ti
-        self._inflight = [recv]  # the receive buffer must outlive the insert
+        self._inflight.append(recv)  # the receive buffer must outlive the insert (until sync())
         self._pending = False
 
     # the Bloom pass over a device image: this rank's ungated local count (super-k-mers: the owners'
@@ -600,7 +601,7 @@ class ShardedCounter:
             tot = torch.tensor([int(nis)], dtype=torch.int64, device=self.device if self.device == "cuda" else "cpu")
             if self.world > 1:
                 self.dist.all_reduce(tot, group=self.group)
-        self._inflight = [recv]  # the receive buffer must outlive the owner's passes
+        self._inflight.append(recv)  # the receive buffer must outlive the owner's passes (until sync())
         self._counted = True
         self._pending = False
         return int(tot.item())

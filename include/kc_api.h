@@ -199,7 +199,15 @@ int kc_insert_keys_device(kc_ctx* ctx, const uint64_t* dev_keys, uint64_t n_keys
  * rank o (all-to-all), and each owner counts what it received with kc_count_packed_device (or runs
  * its Bloom pass 1 over it with kc_bloom_packed_device, then kc_bloom_finalize and the counting
  * pass): the concatenated streams of every sender, n_words words, readable for n_words + 2 words;
- * `windows` = the windows they hold (sizes the partition levels; 0 = unknown).  Replaces the
+ * `windows` = the windows they hold, a hint (0 = unknown) that only chooses the length of the batches
+ * the stream is cut into (about a staging batch's windows each if the stream is uniform).  It sizes
+ * no buffer: every batch's windows are counted on the device before its partition levels are sized
+ * (one read of the break words and one host wait per call), so any value gives the same table, and
+ * a stream whose windows cluster (mixed read lengths, runs of N) is as safe as a uniform one.  A hint
+ * far below the truth makes long batches, which may end in KC_ERR_NOMEM.
+ * kc_packed_windows_device is that counter on its own: *windows = the windows of dev_bk[0 .. n_words),
+ * i.e. the sum of max(0, L - k + 1) over its maximal break-free runs of L symbols (the word before
+ * the range counts as a break; dev_pk is not read); it waits for the stream.  Replaces the
  * reference's one shared table (kmer_hash_table.cpp:2207-2567) with one table per owner. */
 int kc_route_superkmers_device(kc_ctx* ctx, const uint8_t* dev_image, const kc_chunk* chunks, size_t n_chunks,
                                int fmt, uint32_t nshards, int m, uint64_t* dev_pk, uint32_t* dev_bk,
@@ -208,6 +216,8 @@ int kc_count_packed_device(kc_ctx* ctx, const uint64_t* dev_pk, const uint32_t* 
                            uint64_t windows, void* hip_stream);
 int kc_bloom_packed_device(kc_ctx* ctx, const uint64_t* dev_pk, const uint32_t* dev_bk, uint64_t n_words,
                            uint64_t windows, void* hip_stream);
+int kc_packed_windows_device(kc_ctx* ctx, const uint64_t* dev_pk, const uint32_t* dev_bk, uint64_t n_words,
+                             void* hip_stream, uint64_t* windows);
 
 /* Pre-aggregated sharding (the multi-GPU path of kaarme_amd.sharded): every rank counts
  * its own input into its own table, then kc_route_table_device writes the table's

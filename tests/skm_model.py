@@ -119,3 +119,41 @@ def route(seqs, k, G, m=0):
         for o, p, r in superkmers(c, k, G, m):
             out[o].append(s[p - k + 1:p + r])
     return out
+
+
+def window_ends(bk, k):
+    """Per symbol of the break words bk: whether a window ends there, i.e. the symbol is no break
+    and has k - 1 break-free predecessors inside the range (the symbol before the range counts as a
+    break, the range ends with its last word): the model of kc_packed_windows_device."""
+    bk = np.asarray(bk, dtype=np.uint32)
+    if len(bk) == 0:
+        return np.zeros(0, dtype=bool)
+    br = ((bk[:, None] >> (31 - np.arange(32, dtype=np.uint32))) & 1).astype(bool).ravel()
+    pos = np.arange(len(br), dtype=np.int64)
+    last = np.maximum.accumulate(np.where(br, pos, -1))  # the last break at or before each symbol
+    return pos - last >= k
+
+
+def packed_windows(bk, k):
+    """Windows of the break words bk: the sum of max(0, L - k + 1) over its break-free runs."""
+    return int(np.count_nonzero(window_ends(bk, k)))
+
+
+def packed_cut_words(batch_bytes, n_words, hint):
+    """The cut length of a packed pass in words (csrc/kc_plan_host.h packed_cut_words)."""
+    dens = min(1.0, 1.15 * float(hint) / (n_words * 32.0) + 1e-3) if hint and n_words else 1.0
+    return max(1024, int(batch_bytes / dens) // 32)
+
+
+def packed_cuts(bk, lim):
+    """First words of the batches kc_count_packed_device cuts a stream into: after at least lim
+    words, at the next word whose first symbol is a break."""
+    bk = np.asarray(bk, dtype=np.uint32)
+    starts = np.flatnonzero(bk >> 31)
+    cuts = [0]
+    while len(bk) - cuts[-1] > lim:
+        i = np.searchsorted(starts, cuts[-1] + lim)
+        if i == len(starts):
+            break
+        cuts.append(int(starts[i]))
+    return cuts

@@ -490,3 +490,57 @@ def test_batch_groups():
         assert sum((c[1] + 4095) // 4096 * 4096 for c in grp) <= 3 * 4096
     with pytest.raises(ValueError):
         batch_groups([(0, 5 * 4096, 0)], 4 * 4096)
+
+
+class _World1:
+    """torch.distributed stand-in of one rank (nothing is initialised, nothing leaves the rank)."""
+
+    @staticmethod
+    def get_world_size(group=None):
+        return 1
+
+    @staticmethod
+    def get_rank(group=None):
+        return 0
+
+
+def test_receive_buffers_of_every_pass_live_until_sync():
+    """Two counting passes before sync(): the received streams of both stay referenced (the owner's
+    kernels may still read the first pass's while the second is queued); sync() releases them."""
+    import gc
+    import weakref
+
+    reads = make_reads(30, 90, seed=3)
+
+    class Engine(NumpyEngine):
+        def __init__(self, *a):
+            super().__init__(*a)
+            self.seen = []
+
+        def count_packed(self, pk, bk, n, windows, stream=0):
+            self.seen.append((weakref.ref(pk), weakref.ref(bk)))
+            super().count_packed(pk, bk, n, windows, stream)
+
+    k = 21
+    eng = Engine(k, reads)
+    sc = ShardedCounter(Config(k=k, mode=0), _World1(), engine=eng, exchange="superkmers")
+    sc.reset()
+    sc.count_device(0, [(0, 15, 0)], 2)
+    sc.count_device(0, [(15, 15, 0)], 2)
+    gc.collect()
+    assert len(eng.seen) == 2
+    assert all(r() is not None for pair in eng.seen for r in pair), "a pass's receive buffer was dropped before sync()"
+    assert eng.seen[0][0]() is not eng.seen[1][0]()
+    sc.sync()
+    gc.collect()
+    assert all(r() is None for pair in eng.seen for r in pair), "sync() keeps receive buffers alive"
+    assert eng.owner.table == collections.Counter(km for r in reads for km in canonical_windows(r, k))
+    # reset(), finish() and close() release them too
+    for release in (sc.reset, sc.finish, sc.close):
+        n = len(eng.seen)
+        sc.count_device(0, [(0, 15, 0)], 2)
+        gc.collect()
+        assert all(r() is not None for r in eng.seen[n])
+        release()
+        gc.collect()
+        assert all(r() is None for r in eng.seen[n]), release.__name__
