@@ -1,13 +1,19 @@
 // kc_api_unitig.cpp -- the unitigs of the counted table's de Bruijn graph (include/kc_api.h
-// kc_unitigs*): the checks, the scratch and the host form.  Kernels: kc_unitig_impl.h (the sweeps
-// that number the nodes and find the successor states, the bases) and kc_unitig.hip (the ranking,
-// the cut of the circles, the records); the host arithmetic: kc_unitig_host.h.
+// kc_unitigs*) and the compacted graph, the unitigs with the edges between them (kc_unitig_graph*):
+// the checks, the scratch and the host forms.  Kernels: kc_unitig_impl.h (the sweeps that number the
+// nodes and find the successor states, the bases, the edges) and kc_unitig.hip (the ranking, the
+// cut of the circles, the records); the host arithmetic: kc_unitig_host.h.
 #include "kc_ctx.h"
 
 #pragma GCC visibility push(hidden)
 
 static_assert(sizeof(kc_unitig) == 32 && sizeof(kc_unitig_stats) == 40, "include/kc_api.h states these sizes");
 static_assert(sizeof(kc_unitig_stats) == 5 * sizeof(unsigned long long), "UC_STATS: five control words");
+static_assert(sizeof(kc_unitig_edge) == 16 && sizeof(kc_cdbg_stats) == 64, "include/kc_api.h states these sizes");
+static_assert(sizeof(kc_cdbg_stats) == (UC_CDBG_ZERO + 1 - UC_STATS) * sizeof(unsigned long long) && UC_CDBG_ZERO < UC_SRC &&
+                  offsetof(kc_cdbg_stats, edges) == (UC_EDGES - UC_STATS) * 8 && offsetof(kc_cdbg_stats, dead_ends) == (UC_DEAD - UC_STATS) * 8,
+              "kc_cdbg_stats is the control words from UC_STATS on");
+static_assert(KC_EDGE_FROM_REV == 1 && KC_EDGE_TO_REV == 2, "k_unitig_edges writes from_rev | to_rev << 1");
 static_assert(sizeof(UnitigState) * 4 + 4 + 8 + 8 + 4 + 4 + 16 == UNITIG_NODE_BYTES, "kc_unitig_host.h counts a node's bytes");
 
 static int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count) {
@@ -41,19 +47,20 @@ UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound) {
 // is reported before any kernel of the call is launched -- then the three sweeps and the jump
 // launches.  Leaves the views and the rounds for unitig_write.
 static int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u,
-                       int* rounds) {
+                       int* rounds, bool with_rec = false) {
     const uint64_t slots = c->nbuckets * (uint64_t)c->S;
     bound = std::max<uint64_t>(1, std::min(bound, slots));
     if (bound >= UNITIG_MAX_BOUND)
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: " + std::to_string(bound) + " node ids do not fit 32-bit states (the "
                                      "device form sizes by the table's slots, kc_unitigs by the k-mers from min_count on)");
     const uint64_t words = unitig_layout(bound).words;
-    if (c->d_graph_edges.capacity() < slots || c->d_unitig_ids.capacity() < slots || c->d_unitig_node.capacity() < words)
-        make_room(c, unitig_scratch_bytes(slots, bound));
+    if (c->d_graph_edges.capacity() < slots || c->d_unitig_ids.capacity() < slots || c->d_unitig_node.capacity() < words ||
+        (with_rec && c->d_unitig_rec.capacity() < bound))
+        make_room(c, unitig_scratch_bytes(slots, bound, with_rec));
     if (!c->d_graph_edges.reserve(slots) || !c->d_unitig_ids.reserve(slots) || !c->d_unitig_node.reserve(words) ||
-        !c->d_unitig_ctl.reserve(UNITIG_CTL_WORDS))
+        !c->d_unitig_ctl.reserve(UNITIG_CTL_WORDS) || (with_rec && !c->d_unitig_rec.reserve(bound)))
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: scratch allocation failed (" +
-                                     std::to_string(unitig_scratch_bytes(slots, bound)) + " bytes)");
+                                     std::to_string(unitig_scratch_bytes(slots, bound, with_rec)) + " bytes)");
     *u = unitig_bufs(c, bound);
     *rounds = unitig_rounds(bound);
     HIPCHK(c, hipMemsetAsync(u->ctl, 0, UNITIG_CTL_WORDS * sizeof(unsigned long long), s));
@@ -63,13 +70,36 @@ static int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64
     return KC_OK;
 }
 
-// the records, the bases and the statistics of a ranking, each where its pointer is not NULL
+// the records, the bases and the statistics of a ranking, each where its pointer is not NULL; rec
+// (kc_unitig_graph*): the record indices this launch hands out, per start id
 static int unitig_write(kc_ctx* c, const UnitigBufs& u, int rounds, kc_unitig* recs, uint64_t cap_unitigs, uint8_t* bases,
-                        uint64_t cap_bases, kc_unitig_stats* dev_stats, hipStream_t s) {
-    HIPCHK(c, launch_unitig_heads(u, c->cfg.k, rounds, recs, cap_unitigs, bases ? cap_bases : 0, s));
+                        uint64_t cap_bases, kc_unitig_stats* dev_stats, hipStream_t s, uint32_t* rec = nullptr) {
+    HIPCHK(c, launch_unitig_heads(u, c->cfg.k, rounds, recs, cap_unitigs, bases ? cap_bases : 0, rec, s));
     if (bases) HIPCHK(c, launch_unitig_emit(table_view(c), c->cfg.k, u, bases, s));
     if (dev_stats)
         HIPCHK(c, hipMemcpyAsync(dev_stats, u.ctl + UC_STATS, sizeof(kc_unitig_stats), hipMemcpyDeviceToDevice, s));
+    return KC_OK;
+}
+
+// the ids' bound of the host forms: the k-mers with T(c) >= min_count (one count-only sweep, as
+// kc_graph's); waits
+static int unitig_bound(kc_ctx* c, uint32_t min_count, unsigned long long* bound) {
+    hipStream_t s = c->stream;
+    int rc = sync_for_read(c);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(&c->d_ctr->dump_n, 0, 16 * 8 * 2, s));  // dump_n + occupied lines
+    HIPCHK(c, launch_dump(table_view(c), c->cfg.mode == 0 ? 0 : 1, min_count ? min_count : 1, nullptr, c->d_ctr, s));
+    HIPCHK(c, hipMemcpyAsync(bound, &c->d_ctr->dump_n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return KC_OK;
+}
+
+// what a host form hands to its caller (who frees it with kc_free): n elements from dev, or an empty block
+template <class T>
+static int unitig_to_host(kc_ctx* c, std::unique_ptr<T, StdFree>* out, const T* dev, uint64_t n, hipStream_t s) {
+    out->reset((T*)std::malloc(std::max<size_t>(1, n * sizeof(T))));
+    if (!*out) return c->fail(KC_ERR_NOMEM, "host allocation failed");
+    if (dev && n) HIPCHK(c, hipMemcpyAsync(out->get(), dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
     return KC_OK;
 }
 
@@ -103,13 +133,8 @@ int kc_unitigs(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** un
     int rc = unitig_check(c, min_count, max_count);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    // the ids' bound: the k-mers with T(c) >= min_count (one count-only sweep, as kc_graph's)
     unsigned long long bound = 0;
-    if ((rc = sync_for_read(c))) return rc;
-    HIPCHK(c, hipMemsetAsync(&c->d_ctr->dump_n, 0, 16 * 8 * 2, s));  // dump_n + occupied lines
-    HIPCHK(c, launch_dump(table_view(c), c->cfg.mode == 0 ? 0 : 1, min_count ? min_count : 1, nullptr, c->d_ctr, s));
-    HIPCHK(c, hipMemcpyAsync(&bound, &c->d_ctr->dump_n, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if ((rc = unitig_bound(c, min_count, &bound))) return rc;
     // rank once, read the totals, allocate, write
     UnitigBufs u;
     int rounds = 0;
@@ -146,6 +171,80 @@ int kc_unitigs(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** un
     drain.done();
     if (unitigs) *unitigs = out_r.release();
     if (bases) *bases = out_b.release();
+    if (stats) *stats = h;
+    return KC_OK;
+}
+
+// ---- the compacted graph: the unitigs and the edges between them (kc_unitig_graph*) -----------------
+int kc_unitig_graph_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs, uint64_t cap_unitigs,
+                           uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
+                           kc_cdbg_stats* stats, void* sp) {
+    if (!c) return KC_ERR_ARG;
+    int rc = unitig_check(c, min_count, max_count);
+    if (rc) return rc;
+    if ((uintptr_t)edges & 15) return c->fail(KC_ERR_ARG, "kc_unitig_graph_device: dev_edges is not 16-byte aligned");
+    hipStream_t s = (hipStream_t)sp;
+    if ((rc = flush_host(c))) return rc;
+    StreamScope on(c, s);
+    if ((rc = on.join())) return rc;
+    if ((rc = materialize_zero(c, s))) return rc;  // an emptied table has no unitigs
+    UnitigBufs u;
+    int rounds = 0;
+    if ((rc = unitig_rank(c, min_count, max_count, c->nbuckets * (uint64_t)c->S, s, &u, &rounds, true))) return rc;
+    // the edges read the record numbering of this heads launch, the one whose records the caller receives
+    if ((rc = unitig_write(c, u, rounds, unitigs, cap_unitigs, bases, cap_bases, nullptr, s, c->d_unitig_rec))) return rc;
+    HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, u, c->d_unitig_rec, edges, cap_edges, s));
+    if (stats) HIPCHK(c, hipMemcpyAsync(stats, u.ctl + UC_STATS, sizeof(kc_cdbg_stats), hipMemcpyDeviceToDevice, s));
+    return on.finish();
+}
+
+int kc_unitig_graph(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+                    kc_unitig_edge** edges, kc_cdbg_stats* stats) {
+    if (!c) return KC_ERR_ARG;
+    if (unitigs) *unitigs = nullptr;
+    if (bases) *bases = nullptr;
+    if (edges) *edges = nullptr;
+    int rc = unitig_check(c, min_count, max_count);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    unsigned long long bound = 0;
+    if ((rc = unitig_bound(c, min_count, &bound))) return rc;
+    // rank once, read the totals (records and edges counted without buffers), allocate, write
+    UnitigBufs u;
+    int rounds = 0;
+    kc_cdbg_stats h{};
+    DevBuf<kc_unitig> dr;
+    DevBuf<uint8_t> db;
+    DevBuf<kc_unitig_edge> de;
+    DrainOnError drain{s};
+    if ((rc = unitig_rank(c, min_count, max_count, bound, s, &u, &rounds, true))) return rc;
+    uint32_t* rec = c->d_unitig_rec;
+    if ((rc = unitig_write(c, u, rounds, nullptr, 0, nullptr, 0, nullptr, s, rec))) return rc;
+    HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, u, rec, nullptr, 0, s));
+    HIPCHK(c, hipMemcpyAsync(&h, u.ctl + UC_STATS, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const bool want_r = unitigs && h.unitigs, want_b = bases && h.bases, want_e = edges && h.edges;
+    if (want_r || want_b || want_e) {
+        make_room(c, h.unitigs * sizeof(kc_unitig) + h.bases + h.edges * sizeof(kc_unitig_edge));
+        if ((want_r && !dr.reserve(h.unitigs)) || (want_b && !db.reserve(h.bases)) || (want_e && !de.reserve(h.edges)))
+            return c->fail(KC_ERR_NOMEM, "kc_unitig_graph: record, base and edge buffer allocation failed");
+        // the records' launch numbers them anew, and the edges after it read that numbering
+        if ((rc = unitig_write(c, u, rounds, want_r ? dr.get() : nullptr, h.unitigs, want_b ? db.get() : nullptr, h.bases,
+                               nullptr, s, rec)))
+            return rc;
+        if (want_e) HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, u, rec, de.get(), h.edges, s));
+    }
+    std::unique_ptr<kc_unitig, StdFree> out_r;
+    std::unique_ptr<uint8_t, StdFree> out_b;
+    std::unique_ptr<kc_unitig_edge, StdFree> out_e;
+    if (unitigs && (rc = unitig_to_host(c, &out_r, want_r ? dr.get() : nullptr, h.unitigs, s))) return rc;
+    if (bases && (rc = unitig_to_host(c, &out_b, want_b ? db.get() : nullptr, h.bases, s))) return rc;
+    if (edges && (rc = unitig_to_host(c, &out_e, want_e ? de.get() : nullptr, h.edges, s))) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));
+    drain.done();
+    if (unitigs) *unitigs = out_r.release();
+    if (bases) *bases = out_b.release();
+    if (edges) *edges = out_e.release();
     if (stats) *stats = h;
     return KC_OK;
 }

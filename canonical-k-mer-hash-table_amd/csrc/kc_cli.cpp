@@ -91,6 +91,11 @@ struct Args {
     std::string unitigs;
     unsigned long long unitigs_min = 0, unitigs_max = 0;
     bool unitigs_min_set = false, unitigs_max_set = false;
+    // --gfa FILE [--gfa-min N] [--gfa-max N]: the compacted graph (kc_unitig_graph) as GFA 1.0, the
+    // unitigs as segments and the edges between them as links; the range as for --graph
+    std::string gfa;
+    unsigned long long gfa_min = 0, gfa_max = 0;
+    bool gfa_min_set = false, gfa_max_set = false;
 };
 
 const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
@@ -142,7 +147,13 @@ void usage(const char* prog) {
                  "                              \" circular\" for a circle, and the bases on one line\n"
                  "  --unitigs-min,--unitigs-max UINT\n"
                  "                              a k-mer is a node when its count is in this range (def. the -a value and\n"
-                 "                              up); needs --unitigs\n\n"
+                 "                              up); needs --unitigs\n"
+                 "  --gfa FILE                  write the compacted de Bruijn graph as GFA 1.0: a segment per unitig\n"
+                 "                              \"S <i> <bases> LN:i:<bases> KC:i:<sum of counts>\", a link per edge\n"
+                 "                              between unitigs \"L <i> <+|-> <j> <+|-> <k-1>M\", and the two links\n"
+                 "                              \"L i + i +\", \"L i - i -\" that close a circular unitig\n"
+                 "  --gfa-min,--gfa-max UINT    a k-mer is a node when its count is in this range (def. the -a value and\n"
+                 "                              up); needs --gfa\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -351,6 +362,13 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 (o == "--unitigs-min" ? a->unitigs_min : a->unitigs_max) = u;
                 (o == "--unitigs-min" ? a->unitigs_min_set : a->unitigs_max_set) = true;
+            } else if (o == "--gfa") {
+                a->gfa = v;
+            } else if (o == "--gfa-min" || o == "--gfa-max") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                (o == "--gfa-min" ? a->gfa_min : a->gfa_max) = u;
+                (o == "--gfa-min" ? a->gfa_min_set : a->gfa_max_set) = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -411,6 +429,10 @@ int parse(int argc, char** argv, Args* a) {
     if (!a->unitigs_min_set) a->unitigs_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
     if (a->unitigs_max && a->unitigs_min > a->unitigs_max)
         return cli_error(kValidation, "--unitigs-min: a minimum above its maximum");
+    if ((a->gfa_min_set || a->gfa_max_set) && a->gfa.empty())
+        return cli_error(kRequires, "--gfa-min/--gfa-max require --gfa");
+    if (!a->gfa_min_set) a->gfa_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if (a->gfa_max && a->gfa_min > a->gfa_max) return cli_error(kValidation, "--gfa-min: a minimum above its maximum");
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -1335,6 +1357,44 @@ int main(int argc, char** argv) {
         std::cout << "Unitigs: " << ust.unitigs << " (" << ust.circular << " circular), " << ust.nodes << " nodes, "
                   << ust.bases << " bases, longest " << ust.max_nodes << " nodes\n";
     }
+    if (!a.gfa.empty()) {  // extension: the compacted graph, unitigs and the edges between them, as GFA 1.0
+        kc_unitig* urec = nullptr;
+        uint8_t* ubases = nullptr;
+        kc_unitig_edge* uedges = nullptr;
+        kc_cdbg_stats cst;
+        if (kc_unitig_graph(ctx, (uint32_t)a.gfa_min, (uint32_t)a.gfa_max, &urec, &ubases, &uedges, &cst) != KC_OK) die("gfa");
+        FILE* f = std::fopen(a.gfa.c_str(), "w");
+        if (!f) {
+            std::cerr << "cannot write " << a.gfa << std::endl;
+            kc_free(urec); kc_free(ubases); kc_free(uedges); kc_destroy(ctx);
+            return 1;
+        }
+        const unsigned long long ov = (unsigned long long)a.k - 1;
+        std::fputs("H\tVN:Z:1.0\n", f);
+        for (uint64_t i = 0; i < cst.unitigs; i++) {
+            const kc_unitig& r = urec[i];
+            const uint64_t len = r.n_nodes + ov;
+            std::fprintf(f, "S\t%llu\t", (unsigned long long)i);
+            std::fwrite(ubases + r.offset, 1, (size_t)len, f);
+            std::fprintf(f, "\tLN:i:%llu\tKC:i:%llu\n", (unsigned long long)len, (unsigned long long)r.count_sum);
+        }
+        for (uint64_t j = 0; j < cst.edges; j++) {
+            const kc_unitig_edge& e = uedges[j];
+            std::fprintf(f, "L\t%u\t%c\t%u\t%c\t%lluM\n", e.from, e.flags & KC_EDGE_FROM_REV ? '-' : '+', e.to,
+                         e.flags & KC_EDGE_TO_REV ? '-' : '+', ov);
+        }
+        for (uint64_t i = 0; i < cst.unitigs; i++)  // a circle's closing link, on either strand
+            if (urec[i].flags & KC_UNITIG_CIRCULAR)
+                std::fprintf(f, "L\t%llu\t+\t%llu\t+\t%lluM\nL\t%llu\t-\t%llu\t-\t%lluM\n", (unsigned long long)i,
+                             (unsigned long long)i, ov, (unsigned long long)i, (unsigned long long)i, ov);
+        kc_free(urec);
+        kc_free(ubases);
+        kc_free(uedges);
+        if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.gfa << std::endl; kc_destroy(ctx); return 1; }
+        std::cout << "Compacted graph: " << cst.unitigs << " unitigs (" << cst.circular << " circular), " << cst.nodes
+                  << " nodes, " << cst.bases << " bases, longest " << cst.max_nodes << " nodes, " << cst.edges
+                  << " edges, " << cst.dead_ends << " dead ends\n";
+    }
     auto t3 = clk::now();
     std::cout << "Time used to build hash table: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count() + (a.use_bf ? 0 : prep_us)
@@ -1346,7 +1406,7 @@ int main(int argc, char** argv) {
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
     if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty() || !a.graph.empty() ||
-        !a.graph_stats.empty() || !a.unitigs.empty())
+        !a.graph_stats.empty() || !a.unitigs.empty() || !a.gfa.empty())
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
                   << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")

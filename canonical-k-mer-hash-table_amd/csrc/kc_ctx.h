@@ -249,10 +249,12 @@ struct kc_ctx {
     DevBuf<uint8_t> d_graph_edges;
     DevBuf<unsigned long long> d_graph_stat;
     // the unitigs (kc_api_unitig.cpp): a node id per table slot, the per-node arrays of UnitigBufs in
-    // one block (unitig_layout), the control words; they grow only
+    // one block (unitig_layout), the control words; they grow only.  d_unitig_rec: the record index
+    // per node id, allocated by kc_unitig_graph* alone
     DevBuf<uint32_t> d_unitig_ids;
     DevBuf<uint64_t> d_unitig_node;
     DevBuf<unsigned long long> d_unitig_ctl;
+    DevBuf<uint32_t> d_unitig_rec;
 
     uint64_t n_chunks = 0, n_bytes = 0;
 

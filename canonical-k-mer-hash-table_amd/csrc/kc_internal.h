@@ -518,7 +518,10 @@ enum : int {
     UC_CYCLE,       // states the first ranking left on cycles
     UC_REC,         // record cursor
     UC_BASE,        // base cursor
-    UC_STATS,       // the five words of kc_unitig_stats (up to UC_STATS + 4)
+    UC_STATS,       // the five words of kc_unitig_stats (up to UC_STATS + 4), then kc_cdbg_stats' three:
+    UC_EDGES = UC_STATS + 5,  // the edge records, and their cursor (k_unitig_edges)
+    UC_DEAD,        // unitig ends without an edge
+    UC_CDBG_ZERO,   // kc_cdbg_stats.reserved
     UC_SRC = 16,
     UC_MOVED = UC_SRC + UNITIG_MAX_LAUNCHES,
     UNITIG_CTL_WORDS = UC_MOVED + UNITIG_MAX_LAUNCHES
@@ -547,14 +550,21 @@ struct UnitigOps {
     static hipError_t succ(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, UnitigBufs u, hipStream_t s);
     // every node's base(s) into bases, bounded per unitig by what k_unitig_heads left in u.off
     static hipError_t emit(TableView t, int k, UnitigBufs u, uint8_t* bases, hipStream_t s);
+    // the edges between unitigs (include/kc_api.h kc_unitig_graph_device): counted into UC_EDGES and
+    // UC_DEAD, and the first `cap` written to out (16 bytes each; nullptr: counted only) with the
+    // record indices the last k_unitig_heads left in rec[start id]
+    static hipError_t edges(TableView t, int k, UnitigBufs u, const uint32_t* rec, void* out, uint64_t cap, hipStream_t s);
 };
 hipError_t launch_unitig_succ(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, UnitigBufs u, hipStream_t s);
 hipError_t launch_unitig_emit(TableView t, int k, UnitigBufs u, uint8_t* bases, hipStream_t s);
+// zeroes UC_EDGES .. UC_CDBG_ZERO first
+hipError_t launch_unitig_edges(TableView t, int k, UnitigBufs u, const uint32_t* rec, void* out, uint64_t cap, hipStream_t s);
 // kc_unitig.hip, no key width: `rounds` jump launches, the cut of the circles, `rounds` more
 hipError_t launch_unitig_rank(UnitigBufs u, int rounds, hipStream_t s);
-// records (nullptr: none), offsets and statistics; zeroes its cursors first
+// records (nullptr: none), offsets and statistics; zeroes its cursors first.  rec (nullptr: none;
+// `bound` entries): rec[start id] = the record index of the unitig, whether its record fits or not
 hipError_t launch_unitig_heads(UnitigBufs u, int k, int rounds, void* records, uint64_t cap_unitigs, uint64_t cap_bases,
-                               hipStream_t s);
+                               uint32_t* rec, hipStream_t s);
 
 // Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip, kc_unitig.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
 // JoinOps, GraphOps, UnitigOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width

@@ -24,7 +24,8 @@
 //                   with the smaller id, c is read forward when that is the one through L, and its
 //                   position is its distance to the start.  The node at position 0 takes a record
 //                   index and a base offset (two atomics per workgroup and tile), writes the record
-//                   if it fits and leaves the offset, bounded by cap_bases, at off[2 start].
+//                   if it fits and leaves the offset, bounded by cap_bases, at off[2 start], and,
+//                   for the edges between unitigs (k_unitig_edges), the record index at rec[start].
 #include "kc_common.h"
 #include "kc_internal.h"
 
@@ -147,7 +148,8 @@ DEV uint64_t block_excl_sum(uint64_t v, uint64_t& total, unsigned long long (&s_
 }
 
 __global__ __launch_bounds__(UT) void k_unitig_heads(UnitigBufs u, int k, int j, uint64_t* __restrict__ records,
-                                                     uint64_t cap_unitigs, uint64_t cap_bases) {
+                                                     uint64_t cap_unitigs, uint64_t cap_bases,
+                                                     uint32_t* __restrict__ rec) {
     const uint64_t n_nodes = unitig_nodes(u), n_states = 2 * n_nodes;
     const UnitigState* __restrict__ F = u.st[u.ctl[UC_SRC + j] & 1];
     __shared__ unsigned long long s_w[UT / 64], s_rec, s_off;
@@ -198,6 +200,7 @@ __global__ __launch_bounds__(UT) void k_unitig_heads(UnitigBufs u, int k, int j,
             }
             u.off[2 * i] = off + len <= cap_bases ? off : UNITIG_NO_OFF;
             u.off[2 * i + 1] = n;
+            if (rec) rec[i] = (uint32_t)idx;  // (ids, and so records, number below 2^30)
             n_unitigs++;
             n_circ += circ;
             n_bases += len;
@@ -252,11 +255,11 @@ hipError_t launch_unitig_rank(UnitigBufs u, int rounds, hipStream_t s) {
 }
 
 hipError_t launch_unitig_heads(UnitigBufs u, int k, int rounds, void* records, uint64_t cap_unitigs, uint64_t cap_bases,
-                               hipStream_t s) {
+                               uint32_t* rec, hipStream_t s) {
     hipError_t e = hipMemsetAsync(u.ctl + UC_REC, 0, (UC_STATS + 5 - UC_REC) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_unitig_heads, dim3(unitig_grid(u.bound)), dim3(UT), 0, s, u, k, 2 * rounds, (uint64_t*)records,
-                       records ? cap_unitigs : 0, cap_bases);
+                       records ? cap_unitigs : 0, cap_bases, rec);
     return hipGetLastError();
 }
 
@@ -266,6 +269,11 @@ hipError_t launch_unitig_succ(TableView t, int k, int count_mode, uint32_t lo, u
 }
 hipError_t launch_unitig_emit(TableView t, int k, UnitigBufs u, uint8_t* bases, hipStream_t s) {
     KC_DISPATCH(UnitigOps, t.W, emit(t, k, u, bases, s));
+}
+hipError_t launch_unitig_edges(TableView t, int k, UnitigBufs u, const uint32_t* rec, void* out, uint64_t cap, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(u.ctl + UC_EDGES, 0, (UC_CDBG_ZERO + 1 - UC_EDGES) * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    KC_DISPATCH(UnitigOps, t.W, edges(t, k, u, rec, out, cap, s));
 }
 
 }  // namespace kc

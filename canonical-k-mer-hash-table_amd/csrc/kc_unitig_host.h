@@ -14,6 +14,8 @@ constexpr uint64_t UNITIG_MAX_BOUND = 1ULL << 30;
 // bytes of scratch per table slot (the edge byte, the slot's id) and per node id that fits: T(c) 4,
 // slot 8, two successors 8, two states in two buffers 96, start 4, position 4, offset and length 16
 constexpr uint64_t UNITIG_SLOT_BYTES = 5, UNITIG_NODE_BYTES = 140;
+// kc_unitig_graph* only: the record index of the unitig that starts at the node id
+constexpr uint64_t UNITIG_REC_BYTES = 4;
 
 // jump launches of one ranking over up to `bound` nodes: ceil(log2(2 * bound)) + 1, round r covers
 // paths of 2^(r + 1) states
@@ -24,10 +26,11 @@ inline int unitig_rounds(uint64_t bound) {
     return lg + 1;
 }
 
-// the scratch of a call, control words aside; 0: it overflows 64 bits
-inline uint64_t unitig_scratch_bytes(uint64_t table_slots, uint64_t bound) {
-    if (table_slots > ~0ULL / UNITIG_SLOT_BYTES || bound > ~0ULL / UNITIG_NODE_BYTES) return 0;
-    const uint64_t a = table_slots * UNITIG_SLOT_BYTES, b = bound * UNITIG_NODE_BYTES;
+// the scratch of a call (with_rec: of kc_unitig_graph*), control words aside; 0: it overflows 64 bits
+inline uint64_t unitig_scratch_bytes(uint64_t table_slots, uint64_t bound, bool with_rec = false) {
+    const uint64_t node = UNITIG_NODE_BYTES + (with_rec ? UNITIG_REC_BYTES : 0);
+    if (table_slots > ~0ULL / UNITIG_SLOT_BYTES || bound > ~0ULL / node) return 0;
+    const uint64_t a = table_slots * UNITIG_SLOT_BYTES, b = bound * node;
     return a + b < a ? 0 : a + b;
 }
 

@@ -14,6 +14,8 @@
 //   k_unitig_emit    every node rebuilds its k-mer from its slot and writes the last base of the
 //                    strand it is read on at offset + k - 1 + position; the node at position 0 writes
 //                    all k.  A unitig whose bases do not fit has UNITIG_NO_OFF for an offset.
+//   k_unitig_edges   (kc_unitig_graph* only) the edges between unitigs: every edge bit of a unitig
+//                    end, the neighbour probed for its slot and mapped to its unitig's record.
 //
 // Plain loads of the table, no atomics on it, every probe bounded by BPR; every store index is a
 // cursor value below `bound`, an id below the node count, or an offset k_unitig_heads bounded.
@@ -180,6 +182,104 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_emit(TableView tv, int k, Un
     }
 }
 
+// The edges between unitigs.  A unitig end is a state without a successor (a circle's states all
+// have one); the edge bits of the node's side there are the edges, side L of a palindromic node
+// aside (its neighbours are side R's).  A tile of GRAPH_T node ids at a time: the count from the
+// edge byte alone, the tile's place behind the cursor UC_EDGES with one atomic, and -- only with
+// `out` -- one probe per edge for the neighbour's slot, then slot -> id -> start -> record index.
+// from_rev: the end's side differs from the one the node is left through as its unitig reads it;
+// to_rev: the facing side is the one the neighbour is left through as its unitig reads it.  A
+// neighbour the table lacks, or an id or start at or above the node count, cannot be on a table
+// that is only read: the record then says UNITIG_NO_ID instead of following it.
+template <int W>
+__global__ __launch_bounds__(GRAPH_T) void k_unitig_edges(TableView tv, int k, UnitigBufs u, const uint32_t* __restrict__ rec,
+                                                          uint4* __restrict__ out, uint64_t cap) {
+    constexpr int S = BUCKET_WORDS / (W + 1);
+    const RollConst rk = make_roll<W>(k, 0, 0);
+    const uint64_t n_nodes = unitig_nodes(u), n_slots = tv.nbuckets * S;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __shared__ unsigned long long s_wt[GRAPH_T / 64], s_base;
+    unsigned long long dead = 0;
+    const uint64_t tiles = (n_nodes + GRAPH_T - 1) / GRAPH_T;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t i = tile * GRAPH_T + threadIdx.x;
+        uint32_t e = 0;  // the edge bits of this node's unitig ends
+        uint64_t slot = NO_SLOT;
+        if (i < n_nodes && (slot = u.slot_of[i]) < n_slots) {
+            const bool end_r = u.succ[2 * i] == UNITIG_END;
+            bool end_l = u.succ[2 * i + 1] == UNITIG_END;
+            if (end_l && !(k & 1)) {  // a palindrome (even k only) has no link, so both its sides end
+                const uint64_t bucket = slot / S;
+                const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS + (slot - bucket * S) * W;
+                uint64_t tk[W], K[W], RC[W];
+#pragma unroll
+                for (int j = 0; j < W; j++) tk[j] = bk[j];
+                from_tkey<W>(tk, K);
+                revcomp<W>(K, rk, RC);
+                if (key_eq<W>(K, RC)) end_l = false;
+            }
+            const uint32_t eb = u.edges[slot];
+            e = (end_r ? eb & 0x0Fu : 0) | (end_l ? eb & 0xF0u : 0);
+            dead += (end_r && !(eb & 0x0Fu)) + (end_l && !(eb & 0xF0u));
+        }
+        const uint32_t mine = (uint32_t)__popc(e);
+        const uint32_t incl = wave_incl_sum(mine);
+        if (lane == 63) s_wt[wid] = incl;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long tot = 0;
+            for (int w = 0; w < GRAPH_T / 64; w++) tot += s_wt[w];
+            s_base = tot ? atomicAdd(u.ctl + UC_EDGES, tot) : 0;
+        }
+        __syncthreads();
+        uint64_t idx = s_base + incl - mine;
+        for (int w = 0; w < wid; w++) idx += s_wt[w];
+        if (out && e && idx < cap) {
+            const uint64_t bucket = slot / S;
+            const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS + (slot - bucket * S) * W;
+            uint64_t K[W], RC[W];
+            {
+                uint64_t tk[W];
+#pragma unroll
+                for (int j = 0; j < W; j++) tk[j] = bk[j];
+                from_tkey<W>(tk, K);
+            }
+            revcomp<W>(K, rk, RC);
+            const bool pal = key_eq<W>(K, RC);
+            const uint32_t st = u.start[i], rev = u.pos[i] >> 31;
+            const uint32_t from = st < n_nodes ? rec[st] : UNITIG_NO_ID;
+#pragma unroll 1
+            for (; e && idx < cap; e &= e - 1, idx++) {
+                const int b = __ffs((int)e) - 1, side = b >> 2;
+                uint64_t t[W];
+                const int ori = neighbor_tkeys<W>(K, RC, b, rk, t);
+                const uint32_t facing = (ori == 0) == (side == 0) ? 1 : 0;
+                const uint64_t ds = graph_probe_slot<W>(tv, t);
+                uint32_t to = UNITIG_NO_ID, to_rev = 0;
+                if (ds != NO_SLOT) {
+                    const uint32_t did = u.id_of_slot[ds];
+                    if (did < n_nodes) {
+                        const uint32_t sd = u.start[did];
+                        if (sd < n_nodes) to = rec[sd];
+                        to_rev = ori == 2 ? 0 : (1 - facing) ^ (u.pos[did] >> 31);
+                    }
+                }
+                const uint32_t from_rev = pal ? 0 : (uint32_t)side ^ rev;
+                out[idx] = make_uint4(from, to, from_rev | to_rev << 1, 0);  // KC_EDGE_FROM_REV, KC_EDGE_TO_REV
+            }
+        }
+        __syncthreads();  // s_wt and s_base are the next tile's too
+    }
+    for (int m = 32; m >= 1; m >>= 1) dead += __shfl_xor(dead, m, 64);
+    if (lane == 0) s_wt[wid] = dead;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        for (int w = 0; w < GRAPH_T / 64; w++) tot += s_wt[w];
+        if (tot) atomicAdd(u.ctl + UC_DEAD, tot);
+    }
+}
+
 template <int W>
 hipError_t UnitigOps<W>::succ(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, UnitigBufs u, hipStream_t s) {
     if (!t.nbuckets) return hipSuccess;
@@ -204,6 +304,16 @@ hipError_t UnitigOps<W>::emit(TableView t, int k, UnitigBufs u, uint8_t* bases, 
     const uint64_t need = (u.bound + GRAPH_T - 1) / GRAPH_T;
     const unsigned grid = (unsigned)(need < GRAPH_BLOCKS ? (need ? need : 1) : GRAPH_BLOCKS);
     hipLaunchKernelGGL(k_unitig_emit<W>, dim3(grid), dim3(GRAPH_T), 0, s, t, k, u, bases);
+    return hipGetLastError();
+}
+
+template <int W>
+hipError_t UnitigOps<W>::edges(TableView t, int k, UnitigBufs u, const uint32_t* rec, void* out, uint64_t cap, hipStream_t s) {
+    if (!t.nbuckets) return hipSuccess;
+    const uint64_t need = (u.bound + GRAPH_T - 1) / GRAPH_T;
+    const unsigned grid = (unsigned)(need < GRAPH_BLOCKS ? (need ? need : 1) : GRAPH_BLOCKS);
+    hipLaunchKernelGGL(k_unitig_edges<W>, dim3(grid), dim3(GRAPH_T), 0, s, t, k, u, rec, (uint4*)(rec ? out : nullptr),
+                       out ? cap : 0);
     return hipGetLastError();
 }
 

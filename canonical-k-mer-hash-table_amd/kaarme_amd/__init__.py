@@ -65,11 +65,17 @@ EXPORTS = (
     "kc_correct_device", "kc_correct",
     "kc_neighbors_device", "kc_neighbors", "kc_graph_device", "kc_graph",
     "kc_unitigs_device", "kc_unitigs",
+    "kc_unitig_graph_device", "kc_unitig_graph",
 )
 # kc_graph* node flags (KC_GRAPH_*): bits 0-7 the edges -- bit y: canon(c[1:] + y) is a node (side
 # R), bit 4 + y: canon(y + c[:-1]) is a node (side L) -- then the two unitig links and the node bit
 GRAPH_LINK_R, GRAPH_LINK_L, GRAPH_NODE = 0x0100, 0x0200, 0x8000
 UNITIG_CIRCULAR = 1  # kc_unitig.flags (KC_UNITIG_CIRCULAR)
+# kc_unitig_edge.flags (KC_EDGE_*): the edge leaves `from` through the start of its string, enters
+# `to` at the end of its string
+EDGE_FROM_REV, EDGE_TO_REV = 1, 2
+# kc_unitig_edge (include/kc_api.h), 16 bytes
+EDGE_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 # kc_table_op* operations (KC_OP_*): on the raw counts ca, cb of a key in a and in b
 OP_INTERSECT_MIN, OP_INTERSECT_SUM, OP_INTERSECT_LEFT, OP_SUBTRACT, OP_COUNTS_SUBTRACT, OP_UNION_SUM, OP_UNION_MAX = range(7)
 OP_NAMES = {"intersect-min": OP_INTERSECT_MIN, "intersect-sum": OP_INTERSECT_SUM, "intersect-left": OP_INTERSECT_LEFT,
@@ -81,6 +87,23 @@ def unitig_strings(records, bases, k: int) -> List[str]:
     """the strings of unitig records (n, 4) {offset, n_nodes, ...}: bases[offset : offset + n_nodes + k - 1]"""
     b = np.ascontiguousarray(bases, dtype=np.uint8).tobytes()
     return [b[int(o):int(o) + int(n) + k - 1].decode("ascii") for o, n in np.asarray(records)[:, :2].tolist()]
+
+
+def gfa_lines(records, bases, edges, k: int) -> List[str]:
+    """The compacted graph as GFA 1.0 lines (without line ends), what the CLI's --gfa writes: the
+    header, "S <i> <bases> LN:i:<n + k - 1> KC:i:<count_sum>" per unitig record in record order,
+    "L <from> <+|-> <to> <+|-> <k - 1>M" per edge (EDGE_DTYPE) in the edges' order, and the two
+    closing links "L i + i +" and "L i - i -" of every circular unitig, in record order."""
+    records = np.asarray(records, dtype=np.uint64).reshape(-1, 4)
+    edges = np.asarray(edges, dtype=EDGE_DTYPE)
+    out = ["H\tVN:Z:1.0"]
+    for i, (s, (_, _, total, _)) in enumerate(zip(unitig_strings(records, bases, k), records.tolist())):
+        out.append(f"S\t{i}\t{s}\tLN:i:{len(s)}\tKC:i:{total}")
+    for a, b, fl in zip(edges["from"].tolist(), edges["to"].tolist(), edges["flags"].tolist()):
+        out.append(f"L\t{a}\t{'-' if fl & EDGE_FROM_REV else '+'}\t{b}\t{'-' if fl & EDGE_TO_REV else '+'}\t{k - 1}M")
+    for i in np.flatnonzero(records[:, 3] & np.uint64(UNITIG_CIRCULAR)).tolist():
+        out += [f"L\t{i}\t{o}\t{i}\t{o}\t{k - 1}M" for o in "+-"]
+    return out
 
 
 class KcError(RuntimeError):
@@ -156,6 +179,22 @@ class kc_unitig_stats(ctypes.Structure):  # 40 bytes
 
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_unitig_edge(ctypes.Structure):  # 16 bytes
+    _fields_ = [(n, ctypes.c_uint32) for n in ("from", "to", "flags", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_cdbg_stats(ctypes.Structure):  # 64 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("unitigs", "circular", "nodes", "bases", "max_nodes", "edges",
+                                               "dead_ends", "reserved")]
+
+    def as_dict(self) -> dict:
+        """the seven statistics (without the reserved word)"""
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:7]}
 
 
 class kc_correct_stat(ctypes.Structure):  # 16 bytes
@@ -275,6 +314,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_unitigs_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, P]),
         "kc_unitigs": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
                              ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(kc_unitig_stats)]),
+        "kc_unitig_graph_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, U64, P, P]),
+        "kc_unitig_graph": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
+                                  ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
+                                  ctypes.POINTER(ctypes.POINTER(kc_unitig_edge)), ctypes.POINTER(kc_cdbg_stats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -897,6 +940,49 @@ class KmerCounter:
         (k - 1) * unitigs) and max_nodes (the longest unitig)."""
         st = kc_unitig_stats()
         self._chk(self.lib.kc_unitigs(self._ctx, min_count, max_count, None, None, ctypes.byref(st)), "kc_unitigs")
+        return st.as_dict()
+
+    # -- the compacted graph: the unitigs and the edges between them (kc_unitig_graph*)
+    def unitig_graph_device(self, min_count: int = 1, max_count: int = 0, unitigs_ptr: int = 0, cap_unitigs: int = 0,
+                            bases_ptr: int = 0, cap_bases: int = 0, edges_ptr: int = 0, cap_edges: int = 0,
+                            stats_ptr: int = 0, stream: int = 0):
+        """unitigs_device plus the edges between the unitigs, all in device memory: a 16-byte
+        kc_unitig_edge {from, to, flags, 0} per edge at edges_ptr (edge j only when j < cap_edges;
+        from and to are record indices of this call's unitig records, flags EDGE_FROM_REV |
+        EDGE_TO_REV) and the 64-byte kc_cdbg_stats, always the full totals, at stats_ptr; each
+        pointer may be 0.  Enqueued on `stream`, no wait."""
+        self._chk(self.lib.kc_unitig_graph_device(self._ctx, min_count, max_count, ctypes.c_void_p(unitigs_ptr or None),
+                                                  cap_unitigs, ctypes.c_void_p(bases_ptr or None), cap_bases,
+                                                  ctypes.c_void_p(edges_ptr or None), cap_edges,
+                                                  ctypes.c_void_p(stats_ptr or None), ctypes.c_void_p(stream or None)),
+                  "kc_unitig_graph_device")
+
+    def unitig_graph(self, min_count: int = 1, max_count: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray, dict]:
+        """(records, bases, edges, statistics): records and bases as unitigs() gives them, edges an
+        EDGE_DTYPE array in an unspecified order whose from and to index the records, the statistics
+        as unitig_graph_stats().  gfa_lines writes them as GFA."""
+        pr, pb, pe = ctypes.POINTER(kc_unitig)(), ctypes.POINTER(ctypes.c_uint8)(), ctypes.POINTER(kc_unitig_edge)()
+        st = kc_cdbg_stats()
+        self._chk(self.lib.kc_unitig_graph(self._ctx, min_count, max_count, ctypes.byref(pr), ctypes.byref(pb),
+                                           ctypes.byref(pe), ctypes.byref(st)), "kc_unitig_graph")
+        try:
+            recs = (np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint64)), shape=(st.unitigs * 4,)).copy()
+                    if st.unitigs else np.zeros(0, dtype=np.uint64))
+            bases = np.ctypeslib.as_array(pb, shape=(st.bases,)).copy() if st.bases else np.zeros(0, dtype=np.uint8)
+            edges = (np.ctypeslib.as_array(ctypes.cast(pe, ctypes.POINTER(ctypes.c_uint32)), shape=(st.edges * 4,)).copy()
+                     if st.edges else np.zeros(0, dtype=np.uint32))
+        finally:
+            self.lib.kc_free(pr)
+            self.lib.kc_free(pb)
+            self.lib.kc_free(pe)
+        return recs.reshape(-1, 4), bases, edges.view(EDGE_DTYPE), st.as_dict()
+
+    def unitig_graph_stats(self, min_count: int = 1, max_count: int = 0) -> dict:
+        """The compacted graph's totals without records, bases or edges: unitig_stats()' five, edges
+        (edge records) and dead_ends (unitig ends without any edge)."""
+        st = kc_cdbg_stats()
+        self._chk(self.lib.kc_unitig_graph(self._ctx, min_count, max_count, None, None, None, ctypes.byref(st)),
+                  "kc_unitig_graph")
         return st.as_dict()
 
     def compact_read(self, info: dict):

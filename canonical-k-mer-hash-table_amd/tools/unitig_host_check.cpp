@@ -33,6 +33,10 @@ int main() {
     CHECK(unitig_scratch_bytes(268435456ULL, 86000000ULL) == 5 * 268435456ULL + 140 * 86000000ULL);
     CHECK(unitig_scratch_bytes(~0ULL, 1) == 0 && unitig_scratch_bytes(1, ~0ULL) == 0);
     CHECK(unitig_scratch_bytes(~0ULL / 5, ~0ULL / 140) == 0);
+    // ... of kc_unitig_graph*: the record index per id on top
+    CHECK(unitig_scratch_bytes(1 << 20, 1000, true) == 5ULL * (1 << 20) + 144 * 1000);
+    CHECK(unitig_scratch_bytes(268435456ULL, 268435456ULL, true) == 149 * 268435456ULL);
+    CHECK(unitig_scratch_bytes(1, ~0ULL / 144 + 1, true) == 0 && unitig_scratch_bytes(1, ~0ULL / 144 + 1) != 0);
     // the layout: disjoint arrays, in order, inside `words`, and within the bytes the header states
     for (uint64_t b : std::vector<uint64_t>{1, 2, 3, 1000, 86000001, UNITIG_MAX_BOUND - 1}) {
         const UnitigLayout l = unitig_layout(b);

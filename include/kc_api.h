@@ -643,6 +643,70 @@ int kc_unitigs_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_un
 int kc_unitigs(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
                kc_unitig_stats* stats);   /* kc_free both */
 
+/* The compacted de Bruijn graph: the unitigs and the edges between them, what BCALM, GGCAT and
+ * Bifrost write as GFA -- segments and their overlaps of k - 1 bases.  All terms are
+ * kc_graph_device's and kc_unitigs_device's: node, range, side, facing side, link(c, s), unitig,
+ * circular.
+ *   orientation   a unitig record U has the string S_U the same call wrote; U+ is S_U, U- is rc(S_U).
+ *   palindromic unitig  S_U == rc(S_U).  The link rule excludes palindromes, so it is a unitig of one
+ *                 node that is its own reverse complement (even k only).  It has one orientation,
+ *                 always written +.
+ *   unitig end    a pair (node c, side s) with link(c, s) false.  An open unitig has two ends -- of a
+ *                 palindromic one only side R counts -- and a circular unitig has none.
+ *   edge          one per set edge bit of a unitig end (c, s): d the neighbour, t the side of d that c
+ *                 sits on (the facing side), U the unitig of c and V the unitig of d.
+ *                 from_rev = 0 when U is left through the end of S_U: the reading of c when left
+ *                 through s (c for R, rc(c) for L) is c's reading inside S_U; else 1.
+ *                 to_rev = 0 when V is entered at the start of S_V: d entered through t (d for t = L,
+ *                 rc(d) for t = R) is d's reading inside S_V; else 1.
+ *                 Both bits are 0 for a palindromic unitig, and side L of a palindromic node reports
+ *                 nothing: its neighbours are the ones on its side R.
+ *   properties    the last k - 1 bases of orient(S_U, from_rev) are the first k - 1 of orient(S_V,
+ *                 to_rev).  The tuples (from, from_rev, to, to_rev) are distinct.  Every edge's mirror
+ *                 (to, !to_rev, from, !from_rev) is in the list (a palindromic unitig's bit stays 0):
+ *                 a hairpin (U, a, U, !a) is its own mirror and appears once, a homopolymer gives
+ *                 (U, +, U, +) and (U, -, U, -).  edges == kc_graph_stats.edge_ends - link_ends - the
+ *                 edge ends on side L of palindromic nodes.  A circle's closing link is a link, not
+ *                 an edge: KC_UNITIG_CIRCULAR says it, the list does not.
+ *   kc_unitig_graph_device  unitigs and bases as kc_unitigs_device writes them, capacity rules
+ *                 included (offsets and record indices are handed out whatever the capacities are).
+ *                 Edge j is written only when j < cap_edges, nothing past it; the edge order is
+ *                 unspecified.  from and to are record indices of this same call's kc_unitig records
+ *                 in their unbounded numbering -- valid numbers also where cap_unitigs cut the
+ *                 records -- and fit 32 bits because ids < 2^30.  *dev_stats always holds the full
+ *                 totals, so a statistics-only call sizes the next one.  dev_unitigs, dev_bases,
+ *                 dev_edges and dev_stats (device memory) may each be NULL; dev_edges is 16-byte
+ *                 aligned, as every device allocation is (else KC_ERR_ARG).
+ *   kc_unitig_graph  the same in host memory of the exact size (free all three with kc_free); any of
+ *                 the four out-pointers may be NULL; waits.  The ranking runs once: rank, read the
+ *                 totals (records and edges counted without buffers), allocate, write.
+ * The *_device rule, the errors, KC_ERR_NOMEM before any kernel of the call and the emptied table
+ * (zero unitigs, zero edges) are kc_unitigs*'s; kc_unitig_graph_device has no host wait.  The table
+ * is only read and no counter of kc_stats changes.  Two kernels follow kc_unitigs_device's: the
+ * records' kernel also leaves each unitig's record index at its first node's id, and one more pass
+ * over the node ids counts the edge bits of every unitig end (no probe) and, with dev_edges, probes
+ * each edge's neighbour once for its slot, hence its unitig.  That index costs 4 bytes per id, which
+ * only these two calls allocate:
+ *   scratch = 5 * table_slots + 144 * ids bytes,  ids as for kc_unitigs* (< 2^30, else KC_ERR_NOMEM). */
+#define KC_EDGE_FROM_REV 1u  /* kc_unitig_edge.flags: the edge leaves `from` through the start of its string */
+#define KC_EDGE_TO_REV   2u  /* kc_unitig_edge.flags: the edge enters `to` at the end of its string */
+typedef struct {            /* 16 bytes */
+    uint32_t from, to;      /* record indices of this call's kc_unitig records */
+    uint32_t flags;         /* KC_EDGE_FROM_REV | KC_EDGE_TO_REV; every other bit 0 */
+    uint32_t reserved;      /* 0 */
+} kc_unitig_edge;
+typedef struct {            /* 64 bytes */
+    uint64_t unitigs, circular, nodes, bases, max_nodes;   /* as kc_unitig_stats */
+    uint64_t edges;         /* edge records */
+    uint64_t dead_ends;     /* unitig ends without any edge */
+    uint64_t reserved;      /* 0 */
+} kc_cdbg_stats;
+int kc_unitig_graph_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig* dev_unitigs,
+                           uint64_t cap_unitigs, uint8_t* dev_bases, uint64_t cap_bases, kc_unitig_edge* dev_edges,
+                           uint64_t cap_edges, kc_cdbg_stats* dev_stats, void* hip_stream);
+int kc_unitig_graph(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+                    kc_unitig_edge** edges, kc_cdbg_stats* stats);   /* kc_free all three */
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
