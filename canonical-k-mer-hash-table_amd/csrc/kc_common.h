@@ -1,6 +1,7 @@
-// kc_common.h -- device helpers shared by the tokenizer (kc_tokenize.hip) and the
-// counting kernels (kc_count.hip): symbol codes, hashing, wave scans, the 2-bit
-// canonical window roller, XXH64 and the table geometry.
+// kc_common.h -- device helpers shared by every device unit (the tokenizer, the counting
+// kernels, and through kc_table_read.h, kc_key.h and kc_block.h the kernels that read the counted
+// table): symbol codes, hashing, wave scans, the 2-bit canonical window roller, XXH64 and the
+// table geometry.
 #pragma once
 #include "kc_internal.h"
 

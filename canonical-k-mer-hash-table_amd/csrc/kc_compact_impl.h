@@ -27,56 +27,15 @@
 // found by probing and comparing reconstructed keys (left/right characters first, as the
 // reference's quick_kmer_slot_check_sus, kmer_hash_table.cpp:2732-2761).
 #pragma once
-#include "kc_common.h"
+#include "kc_block.h"
+#include "kc_key.h"
+#include "kc_table_read.h"
 
 namespace kc {
 
 constexpr uint64_t CW_OCC = 1, CW_PRED = 2, CW_SELF = 16, CW_PREDC = 32;
 constexpr int CW_RIGHT = 8, CW_LEFT = 10, CW_CNT = 12, CW_PTR = 26;
 constexpr uint64_t CW_NONE = ~0ULL;  // src[] of an empty compact slot
-
-template <int W>
-DEV uint32_t key_char(const uint64_t (&K)[W], int k, int j) {  // character j (0 = leftmost)
-    const int pos = 2 * (k - 1 - j);
-    const int wi = W - 1 - (pos >> 6);
-    uint64_t w = 0;
-#pragma unroll
-    for (int i = 0; i < W; i++)
-        if (i == wi) w = K[i];
-    return (uint32_t)(w >> (pos & 63)) & 3;
-}
-template <int W>
-DEV void or_char(uint64_t (&K)[W], int k, int j, uint32_t c) {
-    const int pos = 2 * (k - 1 - j);
-    const int wi = W - 1 - (pos >> 6);
-#pragma unroll
-    for (int i = 0; i < W; i++)
-        if (i == wi) K[i] |= (uint64_t)c << (pos & 63);
-}
-// P = c followed by the first k - 1 characters of X
-template <int W>
-DEV void prepend_char(const uint64_t (&X)[W], uint32_t c, const RollConst& rk, uint64_t (&P)[W]) {
-#pragma unroll
-    for (int i = W - 1; i >= 1; i--) P[i] = (X[i] >> 2) | (X[i - 1] << 62);
-    P[0] = X[0] >> 2;
-#pragma unroll
-    for (int i = 0; i < W; i++)
-        if (i == rk.rc_word) P[i] |= (uint64_t)c << rk.rc_bit;
-}
-template <int W>
-DEV bool key_le(const uint64_t (&a)[W], const uint64_t (&b)[W]) {
-#pragma unroll
-    for (int i = 0; i < W; i++)
-        if (a[i] != b[i]) return a[i] < b[i];
-    return true;
-}
-template <int W>
-DEV bool key_eq(const uint64_t (&a)[W], const uint64_t (&b)[W]) {
-    bool eq = true;
-#pragma unroll
-    for (int i = 0; i < W; i++) eq &= a[i] == b[i];
-    return eq;
-}
 
 // the minimizer's strand: true if the smallest-hash canonical m-mer (m odd: no palindromes)
 // reads forward in the canonical k-mer K
@@ -178,8 +137,7 @@ __global__ __launch_bounds__(256) void k_cplace(TableView tv, CompactView cv) {
     const int s = (int)(g % S);
     const uint64_t t0 = b[s * W];
     if (t0 == EMPTY) return;
-    const uint64_t c = b[S * W + s] & CNT_MASK;
-    const uint64_t word = CW_OCC | ((c < 16383 ? c : 16383) << CW_CNT);
+    const uint64_t word = CW_OCC | ((uint64_t)tc_of(b[S * W + s], 1) << CW_CNT);
     uint64_t p = cslot_of(t0, cv.nslots);
     while (atomicCAS(reinterpret_cast<unsigned long long*>(cv.words + p), 0ULL, (unsigned long long)word) != 0ULL)
         p = p + 1 == cv.nslots ? 0 : p + 1;
@@ -188,39 +146,19 @@ __global__ __launch_bounds__(256) void k_cplace(TableView tv, CompactView cv) {
 }
 
 // compact slot holding table key tk, or CW_NONE (build): the key is looked up in the
-// full-key table, whose probe sequence (the key's region, buckets from its start bucket,
-// kc_common.h) ends at the first bucket with a free slot, so a missing predecessor costs one
-// or two 128-byte bucket reads instead of a compact-array probe run at load 0.8 (each probe
-// comparing a random bucket's key); the found slot maps to its compact slot through inv.
+// full-key table (table_probe, kc_table_read.h), so a missing predecessor costs one or two
+// 128-byte bucket reads instead of a compact-array probe run at load 0.8 (each probe comparing
+// a random bucket's key); the found slot maps to its compact slot through inv.
 template <int W>
 DEV uint64_t cfind_built(const TableView& tv, const CompactView& cv, const uint64_t (&tk)[W]) {
-    constexpr int S = BUCKET_WORDS / (W + 1);
-    const uint64_t region = region_of(tk[0], tv.R);
-    uint32_t b = bucket_in_region(tk[0], tv.R);
-    for (int probe = 0; probe < BPR; probe++) {
-        const uint64_t bucket = region * BPR + b;
-        const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS;
-        bool free = false;
-#pragma unroll
-        for (int sl = 0; sl < S; sl++) {
-            const uint64_t w0 = bk[sl * W];
-            free |= w0 == EMPTY;
-            if (w0 != tk[0]) continue;
-            bool eq = true;
-#pragma unroll
-            for (int i = 1; i < W; i++) eq &= bk[sl * W + i] == tk[i];
-            if (eq) return cv.inv[bucket * S + sl];
-        }
-        if (free) return CW_NONE;
-        b = (b + 1) & (BPR - 1);
-    }
-    return CW_NONE;
+    return table_probe<W>(tv, tk, CW_NONE, [&](uint64_t bucket, const uint64_t*, int sl) {
+        return cv.inv[bucket * (BUCKET_WORDS / (W + 1)) + sl];
+    });
 }
 
 // k_clink: orientation, predecessor and flags of every compact slot; chain starts -> secondary
 template <int W>
 __global__ __launch_bounds__(256) void k_clink(TableView tv, CompactView cv, int k, int m) {
-    constexpr int S = BUCKET_WORDS / (W + 1);
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint64_t g = p < cv.nslots ? cv.src[p] : CW_NONE;
     const RollConst rk = make_roll<W>(k, 0, 0);
@@ -228,9 +166,7 @@ __global__ __launch_bounds__(256) void k_clink(TableView tv, CompactView cv, int
     bool start = false;
     if (g != CW_NONE) {
         uint64_t t[W];
-        const uint64_t* key = tv.buckets + (g / S) * BUCKET_WORDS + (g % S) * W;
-#pragma unroll
-        for (int i = 0; i < W; i++) t[i] = key[i];
+        slot_tkey<W>(tv, g, t);
         from_tkey<W>(t, K);
         uint64_t rcK[W], X[W];
         revcomp<W>(K, rk, rcK);
@@ -271,15 +207,8 @@ __global__ __launch_bounds__(256) void k_clink(TableView tv, CompactView cv, int
         }
     }
     // chain starts: one atomic per wave for their secondary-array indices
-    const uint64_t ballot = __ballot(start);
-    const int lane = threadIdx.x & 63;
-    unsigned long long base = 0;
-    if (ballot) {
-        if (lane == __ffsll((long long)ballot) - 1) base = atomicAdd(cv.n_second, (unsigned long long)__popcll(ballot));
-        base = __shfl(base, __ffsll((long long)ballot) - 1, 64);
-    }
+    const uint64_t idx = wave_reserve(start, cv.n_second);
     if (start) {
-        const uint64_t idx = base + __popcll(ballot & ((1ULL << lane) - 1));
 #pragma unroll
         for (int i = 0; i < W; i++) cv.second[idx * W + i] = K[i];
         word |= idx << CW_PTR;
@@ -341,15 +270,10 @@ __global__ __launch_bounds__(256) void k_creco(CompactView cv, int k, uint64_t a
     uint32_t hops = 0;
     bool ok = true;
     if (emit) ok = reco<W>(cv, p, k, K, hops);
-    const uint64_t ballot = __ballot(emit);
     const int lane = threadIdx.x & 63;
-    unsigned long long base = 0;
-    if (ballot && out) {
-        if (lane == __ffsll((long long)ballot) - 1) base = atomicAdd(cursor, (unsigned long long)__popcll(ballot));
-        base = __shfl(base, __ffsll((long long)ballot) - 1, 64);
-    }
+    const uint64_t idx = wave_reserve(emit && out, cursor);
     if (emit && out) {
-        uint64_t* o = out + (base + __popcll(ballot & ((1ULL << lane) - 1))) * (W + 1);
+        uint64_t* o = out + idx * (W + 1);
 #pragma unroll
         for (int i = 0; i < W; i++) o[i] = K[i];
         o[W] = cnt;

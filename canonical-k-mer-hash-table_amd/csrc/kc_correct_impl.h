@@ -18,7 +18,8 @@
 // -DKC_CORRECT_NO_PREFILTER builds the kernel without stage 1 (every candidate, all three
 // alternatives, goes to stage 2): the form measured against in DESIGN.md 3a.
 //
-// Like the lookups the kernel only reads the table: plain loads, the READY flag masked.
+// Like the lookups the kernel only reads the table (kc_table_read.h): plain loads, the READY flag
+// masked.
 #pragma once
 #include "kc_correct_seq.h"
 #include "kc_query_impl.h"

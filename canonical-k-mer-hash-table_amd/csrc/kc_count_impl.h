@@ -37,6 +37,7 @@
 
 #include "kc_common.h"
 #include "kc_table_insert.h"
+#include "kc_table_read.h"
 
 namespace kc {
 
@@ -1248,19 +1249,6 @@ __global__ __launch_bounds__(COUNT_THREADS) void k_insert_keys(const uint64_t* _
 // shard merge (pre-aggregated sharding): a rank's table -> {table key, count} records
 // grouped by owner shard; the owner adds the counts into its own table.
 // --------------------------------------------------------------------------------
-// one 128-byte bucket into registers: eight 16-byte loads issued together
-DEV void load_bucket(const uint64_t* __restrict__ b, uint64_t (&bw)[BUCKET_WORDS]) {
-    const uint4* b4 = reinterpret_cast<const uint4*>(b);
-    uint4 v[BUCKET_WORDS / 2];
-#pragma unroll
-    for (int c = 0; c < BUCKET_WORDS / 2; c++) v[c] = b4[c];
-#pragma unroll
-    for (int c = 0; c < BUCKET_WORDS / 2; c++) {
-        bw[2 * c] = ((uint64_t)v[c].y << 32) | v[c].x;
-        bw[2 * c + 1] = ((uint64_t)v[c].w << 32) | v[c].z;
-    }
-}
-
 // SCATTER = false: per-block record counts per owner ([owner][block] into hist);
 // true: records {W table-key words, raw count} at off[owner][block] + rank.
 template <int W, bool SCATTER>
@@ -2259,12 +2247,12 @@ __global__ __launch_bounds__(256) void k_dump(TableView tv, int count_mode, uint
         tv_c[s] = 0;
         if (bkt < tv.nbuckets && bw[s * W] != EMPTY) {
             occ++;
-            const uint64_t c = bw[S * W + s] & CNT_MASK;
-            const uint64_t t = count_mode == 0 ? (c & 0xFFFF) : (c < 16383 ? c : 16383);
+            const uint64_t t = tc_of(bw[S * W + s], count_mode);
             if (t >= min_abundance) { emit[s] = true; tv_c[s] = t; nout++; }
         }
     }
-    // output positions: one atomic per workgroup (not per wave) on the shared cursor
+    // output positions: one atomic per workgroup (not per wave) on the shared cursor (block_reserve
+    // of kc_block.h written out: calling it here reorders this kernel's code, which stays as it is)
     __shared__ unsigned long long s_wt[4], s_base;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint32_t incl = wave_incl_sum(nout);
@@ -2316,8 +2304,7 @@ DEV uint32_t text_bucket(const TableView& tv, uint64_t bkt, int count_mode, uint
     for (int s = 0; s < S; s++) {
         tc[s] = 0;
         if (bkt < tv.nbuckets && bw[s * W] != EMPTY) {
-            const uint64_t c = bw[S * W + s] & CNT_MASK;
-            const uint64_t t = count_mode == 0 ? (c & 0xFFFF) : (c < 16383 ? c : 16383);
+            const uint64_t t = tc_of(bw[S * W + s], count_mode);
             if (t >= a) {
                 tc[s] = (uint32_t)t;
                 bytes += (uint32_t)k + 2 + ndigits((uint32_t)t);

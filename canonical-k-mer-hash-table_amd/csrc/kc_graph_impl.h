@@ -6,24 +6,25 @@
 // table from the output text to ask what follows a k-mer.
 //
 // The table keys are bijective (from_tkey), so a slot gives its canonical k-mer K; from K and
-// rc(K), computed once per k-mer, the eight neighbours come from shifts alone (neighbor_tkeys):
-// K[1:] + y is K shifted left one character with y appended, and its reverse complement is
-// rc(K) shifted right with 3 - y prepended (prepend_char, kc_compact_impl.h); the L side is the
-// mirror image.  No neighbour is reverse-complemented on its own.  A thread forms and probes one
-// neighbour at a time (W goes up to 15 words).
+// rc(K), computed once per k-mer, the eight neighbours come from shifts alone (neighbor_tkeys,
+// kc_key.h): K[1:] + y is K shifted left one character with y appended, and its reverse complement
+// is rc(K) shifted right with 3 - y prepended; the L side is the mirror image.  No neighbour is
+// reverse-complemented on its own.  A thread forms and probes one neighbour at a time (W goes up
+// to 15 words).
 //
-// All three kernels only read the table and are ordered after the counting passes: plain loads,
-// no atomics, no READY spinning, as kc_query_impl.h argues.  Every probe is bounded by BPR buckets.
+// All three kernels only read the table, by the rules of kc_table_read.h: plain loads, every probe
+// bounded by BPR buckets.
 //
 //   k_graph_edges  sweeps the table and, for every node (an occupied slot with lo <= T(c) <= hi),
-//                  probes its eight neighbours (join_probe) and writes one edge byte, bit y = side
-//                  R, bit 4 + y = side L, into edges[bucket * S + slot] (0 for every other slot).
+//                  probes its eight neighbours (table_count_word) and writes one edge byte, bit y =
+//                  side R, bit 4 + y = side L, into edges[bucket * S + slot] (0 for every other slot).
 //   k_graph_links  a second launch on the same stream: it reads the edge bytes and never writes
 //                  them.  For each side of degree 1 of a node it forms that one neighbour again,
 //                  probes for its slot (graph_probe_slot), reads the neighbour's edge byte and
 //                  applies the link rule; statistics are reduced per workgroup (one atomic per
 //                  non-zero field) and the records of a tile of slots are appended behind one
-//                  cursor, one atomic per workgroup and tile, bounded by the caller's capacity.
+//                  cursor, one atomic per workgroup and tile (block_reserve, kc_block.h), bounded
+//                  by the caller's capacity.
 //
 // The sweeps take one slot per thread: a bucket per thread (as k_join sweeps) serialises the S * 8
 // probes of a bucket in one lane.  On a C2 table with every k-mer a node the slot form is faster
@@ -31,80 +32,29 @@
 // the bucket form wins by a tenth where four of ten occupied slots are skipped (T(c) >= 2 at k = 31
 // and 51).  DESIGN.md 3a has the figures; -DKC_GRAPH_BUCKET_MAP builds the bucket form.
 #pragma once
-#include "kc_common.h"
-#include "kc_compact_impl.h"
-#include "kc_join_impl.h"
-#include "kc_query_impl.h"
+#include "kc_block.h"
+#include "kc_key.h"
+#include "kc_table_read.h"
 
 namespace kc {
 
-constexpr int GRAPH_T = 256;
+constexpr int GRAPH_T = BLOCK_T;
 constexpr uint64_t GRAPH_BLOCKS = 8192;  // grid-stride: 32 workgroups per CU
 #ifdef KC_GRAPH_BUCKET_MAP
 constexpr bool GRAPH_BUCKET_MAP = true;
 #else
 constexpr bool GRAPH_BUCKET_MAP = false;
 #endif
-constexpr uint64_t NO_SLOT = ~0ULL;
 // the words of the statistics scratch: the ten of kc_graph_stats, then the record cursor
 constexpr int GS_CURSOR = 10;
 static_assert(GS_CURSOR + 1 == GRAPH_STAT_WORDS, "kc_internal.h states the scratch's size");
 
-// X[1:] + c: X shifted left one character, c appended
-template <int W>
-DEV void append_char(const uint64_t (&X)[W], uint32_t c, const RollConst& rk, uint64_t (&P)[W]) {
-#pragma unroll
-    for (int i = 0; i < W - 1; i++) P[i] = (X[i] << 2) | (X[i + 1] >> 62);
-    P[W - 1] = (X[W - 1] << 2) | c;
-    P[0] &= rk.topmask;
-}
-
-// Neighbour i of the k-mer K (RC its reverse complement): i = y on side R, z = K[1:] + y, and
-// i = 4 + y on side L, z = y + K[:-1].  t = the table key of canon(z).  Returns 0 when z is the
-// canonical form (z < rc(z)), 1 when rc(z) is, 2 when z is its own reverse complement.
-template <int W>
-DEV int neighbor_tkeys(const uint64_t (&K)[W], const uint64_t (&RC)[W], int i, const RollConst& rk, uint64_t (&t)[W]) {
-    const uint32_t y = (uint32_t)i & 3;
-    uint64_t z[W], rz[W];
-    if (i < 4) {
-        append_char<W>(K, y, rk, z);
-        prepend_char<W>(RC, 3 - y, rk, rz);
-    } else {
-        prepend_char<W>(K, y, rk, z);
-        append_char<W>(RC, 3 - y, rk, rz);
-    }
-    const bool le = key_le<W>(z, rz), ge = key_le<W>(rz, z);
-    uint64_t d[W];
-#pragma unroll
-    for (int j = 0; j < W; j++) d[j] = le ? z[j] : rz[j];
-    to_tkey<W>(d, t);
-    return le ? (ge ? 2 : 0) : 1;
-}
-
 // the slot (bucket * S + slot) of table key t in tv, NO_SLOT when the table does not hold it
 template <int W>
 DEV uint64_t graph_probe_slot(const TableView& tv, const uint64_t (&t)[W]) {
-    constexpr int S = BUCKET_WORDS / (W + 1);
-    const uint64_t region = region_of(t[0], tv.R);
-    uint32_t b = bucket_in_region(t[0], tv.R);
-    for (int probe = 0; probe < BPR; probe++) {
-        const uint64_t bucket = region * BPR + b;
-        const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS;
-        bool free = false;
-#pragma unroll
-        for (int sl = 0; sl < S; sl++) {
-            const uint64_t w0 = bk[sl * W];
-            free |= w0 == EMPTY;
-            if (w0 != t[0]) continue;
-            bool eq = true;
-#pragma unroll
-            for (int i = 1; i < W; i++) eq &= bk[sl * W + i] == t[i];
-            if (eq) return bucket * S + sl;
-        }
-        if (free) return NO_SLOT;
-        b = (b + 1) & (BPR - 1);
-    }
-    return NO_SLOT;
+    return table_probe<W>(tv, t, NO_SLOT, [](uint64_t bucket, const uint64_t*, int sl) {
+        return bucket * (BUCKET_WORDS / (W + 1)) + sl;
+    });
 }
 
 // ---- k_neighbors: counts[8 i + j] = T of neighbour j of key i ------------------------------------
@@ -137,7 +87,7 @@ __global__ __launch_bounds__(GRAPH_T) void k_neighbors(TableView tv, int k, int 
             uint64_t t[W];
             neighbor_tkeys<W>(K, RC, j, rk, t);
             bool found;
-            const uint64_t cw = join_probe<W>(tv, t, found);
+            const uint64_t cw = table_count_word<W>(tv, t, found);
             if (found) c = tc_of(cw, count_mode);
         }
         out[j] = c;
@@ -169,7 +119,7 @@ DEV void graph_sweep(const TableView& tv, F&& f, G&& tile_end) {
             const bool in = it < n_items;
             uint64_t bw[BUCKET_WORDS];
             if (in) {
-                query_load_bucket(tv.buckets + it * BUCKET_WORDS, bw);
+                load_bucket(tv.buckets + it * BUCKET_WORDS, bw);
             } else {
 #pragma unroll
                 for (int i = 0; i < BUCKET_WORDS; i++) bw[i] = 0;
@@ -188,11 +138,13 @@ DEV void graph_sweep(const TableView& tv, F&& f, G&& tile_end) {
                 const bool in = it < n_items;
                 const uint64_t bucket = it / S;
                 const int sl = (int)(it - bucket * S);
-                const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS;
                 uint64_t tk[W];
+                // past the end slot 0's words, then zeroed: the loads under `if (in)` cost
+                // k_unitig_succ<3> and <7> an occupancy step (profiles/table_read_resources.md)
+                slot_tkey<W>(tv, in ? it : 0, tk);
 #pragma unroll
-                for (int i = 0; i < W; i++) tk[i] = in ? bk[sl * W + i] : 0;
-                const uint64_t cw = in ? bk[S * W + sl] : 0;
+                for (int i = 0; i < W; i++) tk[i] = in ? tk[i] : 0;
+                const uint64_t cw = in ? tv.buckets[bucket * BUCKET_WORDS + S * W + sl] : 0;
                 f(in, it, tk, cw, j);
             }
         }
@@ -218,7 +170,7 @@ __global__ __launch_bounds__(GRAPH_T) void k_graph_edges(GraphArgs g) {
         [&](bool in, uint64_t slot, const uint64_t (&tk)[W], uint64_t cw, int) {
             if (!in) return;
             uint32_t e = 0;
-            if (tk[0] != EMPTY && join_in_range(tc_of(cw, g.count_mode), g.lo, g.hi)) {
+            if (tk[0] != EMPTY && in_range(tc_of(cw, g.count_mode), g.lo, g.hi)) {
                 uint64_t K[W], RC[W];
                 from_tkey<W>(tk, K);
                 revcomp<W>(K, rk, RC);
@@ -227,8 +179,8 @@ __global__ __launch_bounds__(GRAPH_T) void k_graph_edges(GraphArgs g) {
                     uint64_t t[W];
                     neighbor_tkeys<W>(K, RC, i, rk, t);
                     bool found;
-                    const uint64_t cwn = join_probe<W>(g.tv, t, found);
-                    if (found && join_in_range(tc_of(cwn, g.count_mode), g.lo, g.hi)) e |= 1u << i;
+                    const uint64_t cwn = table_count_word<W>(g.tv, t, found);
+                    if (found && in_range(tc_of(cwn, g.count_mode), g.lo, g.hi)) e |= 1u << i;
                 }
             }
             g.edges[slot] = (uint8_t)e;
@@ -236,37 +188,15 @@ __global__ __launch_bounds__(GRAPH_T) void k_graph_edges(GraphArgs g) {
         [] {});
 }
 
-// the workgroup's sums of the ten statistics, one atomic per non-zero sum
-DEV void graph_block_add(const unsigned long long (&v)[GS_CURSOR], unsigned long long* st) {
-    __shared__ unsigned long long s_red[GS_CURSOR][GRAPH_T / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < GS_CURSOR; q++) {
-        unsigned long long x = v[q];
-        for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-        if (lane == 0) s_red[q][wid] = x;
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < GS_CURSOR) {
-        unsigned long long x = 0;
-#pragma unroll
-        for (int w = 0; w < GRAPH_T / 64; w++) x += s_red[t][w];
-        if (x) atomicAdd(st + t, x);
-    }
-}
-
 template <int W>
 __global__ __launch_bounds__(GRAPH_T) void k_graph_links(GraphArgs g) {
     constexpr int S = BUCKET_WORDS / (W + 1);
     const RollConst rk = make_roll<W>(g.k, 0, 0);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     // a tile's records wait here for the tile's place: {slot's T(c) | flags << 32} of call r of thread
     // t at [r][t] (0: no node; only thread t reads it back), so the cursor takes one atomic per
     // tile -- one per wave and iteration, 4 M of them on a C2 table, took 43 ms of one word's
     // ~90 atomics per microsecond
     __shared__ uint64_t s_rec[GRAPH_RPT][GRAPH_T];
-    __shared__ unsigned long long s_wt[GRAPH_T / 64], s_base;
     unsigned long long n_nodes = 0, n_edge = 0, n_link = 0, n_iso = 0, n_pal = 0, sd0 = 0, sd1 = 0, sd2 = 0, sd3 = 0,
                        sd4 = 0;
     uint32_t mine = 0;        // this thread's nodes of the tile
@@ -276,7 +206,7 @@ __global__ __launch_bounds__(GRAPH_T) void k_graph_links(GraphArgs g) {
         g.tv,
         [&](bool in, uint64_t slot, const uint64_t (&tk)[W], uint64_t cw, int r) {
             const uint32_t tc = tc_of(cw, g.count_mode);
-            const bool node = in && tk[0] != EMPTY && join_in_range(tc, g.lo, g.hi);
+            const bool node = in && tk[0] != EMPTY && in_range(tc, g.lo, g.hi);
             uint32_t flags = 0;
             if (node) {
                 uint64_t K[W], RC[W];
@@ -318,28 +248,15 @@ __global__ __launch_bounds__(GRAPH_T) void k_graph_links(GraphArgs g) {
         [&] {
             if (!g.records) return;
             // the tile's place in the records: one atomic per workgroup and tile
-            const uint32_t incl = wave_incl_sum(mine);
-            if (lane == 63) s_wt[wid] = incl;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                unsigned long long tot = 0;
-                for (int w = 0; w < GRAPH_T / 64; w++) tot += s_wt[w];
-                s_base = tot ? atomicAdd(g.stats + GS_CURSOR, tot) : 0;
-            }
-            __syncthreads();
-            uint64_t idx = s_base + incl - mine;
-            for (int w = 0; w < wid; w++) idx += s_wt[w];
+            uint64_t idx = block_reserve(mine, g.stats + GS_CURSOR);
             constexpr int RPT = GRAPH_BUCKET_MAP ? S : GRAPH_ITERS;
 #pragma unroll 1
             for (int r = 0; r < RPT && mine; r++) {
                 const uint64_t v = s_rec[r][threadIdx.x];
                 if (!v) continue;
                 if (idx < g.capacity) {  // the key again from the table (the tile's lines are in L2)
-                    const uint64_t slot = first_slot + (uint64_t)r * step, bucket = slot / S;
-                    const uint64_t* bk = g.tv.buckets + bucket * BUCKET_WORDS + (slot - bucket * S) * W;
                     uint64_t tk[W], K[W];
-#pragma unroll
-                    for (int i = 0; i < W; i++) tk[i] = bk[i];
+                    slot_tkey<W>(g.tv, first_slot + (uint64_t)r * step, tk);
                     from_tkey<W>(tk, K);
                     uint64_t* o = g.records + idx * (W + 1);
 #pragma unroll
@@ -349,10 +266,13 @@ __global__ __launch_bounds__(GRAPH_T) void k_graph_links(GraphArgs g) {
                 idx++;
             }
             mine = 0;
-            __syncthreads();  // s_wt and s_base are the next tile's too
+            __syncthreads();  // block_reserve's shared words are the next tile's too
         });
     const unsigned long long v[GS_CURSOR] = {n_nodes, n_edge, n_link, n_iso, n_pal, sd0, sd1, sd2, sd3, sd4};
-    graph_block_add(v, g.stats);
+    unsigned long long* dst[GS_CURSOR];
+#pragma unroll
+    for (int q = 0; q < GS_CURSOR; q++) dst[q] = g.stats + q;
+    block_sum_add<GS_CURSOR>(v, dst);
 }
 
 template <int W>

@@ -3,31 +3,21 @@
 // count-of-counts (abundance spectrum) of the whole table.  The reference has no counterpart:
 // its table is only ever walked by the writers (kmer_hash_table.cpp:4318-4524).
 //
-// Both kernels only read the table.  They are ordered after the counting passes, so every
-// stored key is published: plain loads, no atomics on the table, no READY spinning (the flag
-// is masked off the count word).
-//
-// A key's probe sequence (kc_common.h: its region, the buckets from its start bucket, wrapping
-// inside the region) ends at the first bucket with a free slot -- the invariant table_insert
-// keeps and cfind_built (kc_compact_impl.h) relies on -- so a lookup is normally one 128-byte
-// bucket read, present or absent.
+// Both kernels only read the table, by the rules of kc_table_read.h: plain loads, and a probe that
+// ends at the first bucket with a free slot, so a lookup is normally one 128-byte bucket read,
+// present or absent.
 //
 // k_lookup has two forms:
 //  * cooperative (W <= 2, the default): a group of 16 lanes reads a bucket as one coalesced
 //    128-byte request, one u64 each, and finds the slot with a wave ballot; the count word is
 //    a lane shuffle away (the group holds the whole bucket).  Every lane first canonicalises
 //    and mixes its own key; the wave then takes 16 steps of four keys (one per group).
-//  * one thread per key (W >= 3, and W <= 2 with -DKC_QUERY_TPK): S <= 4 strided key loads per
-//    bucket, the count word only on a hit.
+//  * one thread per key (W >= 3, and W <= 2 with -DKC_QUERY_TPK): lookup_thread, S <= 4 strided
+//    key loads per bucket, the count word only on a hit.
 #pragma once
-#include "kc_common.h"
+#include "kc_table_read.h"
 
 namespace kc {
-
-DEV uint32_t tc_of(uint64_t cw, int count_mode) {  // T(c) as k_dump computes it
-    const uint64_t c = cw & CNT_MASK;
-    return (uint32_t)(count_mode == 0 ? (c & 0xFFFF) : (c < 16383 ? c : 16383));
-}
 
 // the table key of query i; false: not a k-mer / not a table key (the answer is 0)
 template <int W>
@@ -49,6 +39,11 @@ DEV bool query_tkey(const uint64_t* __restrict__ keys, uint64_t i, int k, int la
     return true;
 }
 
+// T(c) of table key t, 0 when the table does not hold it.  table_probe's loop (kc_table_read.h),
+// kept here as a loop of its own: through table_probe the address arithmetic of k_seq_counts and
+// k_correct_try comes out differently (no other register count, but correct_time.py's figures
+// 0.5 - 1.6 % up, outside the parent's own spread); with this loop the query, sequence and
+// correction units compile to the code they had.
 template <int W>
 DEV uint32_t lookup_thread(const TableView& tv, const uint64_t (&t)[W], int count_mode) {
     constexpr int S = BUCKET_WORDS / (W + 1);
@@ -84,7 +79,8 @@ __global__ __launch_bounds__(256) void k_lookup_tpk(TableView tv, int k, int cou
     counts[i] = ok ? lookup_thread<W>(tv, t, count_mode) : 0;
 }
 
-// cooperative form: 16 lanes per bucket, four keys per wave per step (W <= 2)
+// cooperative form: 16 lanes per bucket, four keys per wave per step (W <= 2); the probe is
+// table_probe's (kc_table_read.h), a bucket across 16 lanes
 template <int W>
 __global__ __launch_bounds__(256) void k_lookup_coop(TableView tv, int k, int count_mode, int layout,
                                                      const uint64_t* __restrict__ keys, uint64_t n,
@@ -130,19 +126,6 @@ __global__ __launch_bounds__(256) void k_lookup_coop(TableView tv, int k, int co
     if (i < n) counts[i] = res;
 }
 
-// one 128-byte bucket into registers: eight 16-byte loads issued together
-DEV void query_load_bucket(const uint64_t* __restrict__ b, uint64_t (&bw)[BUCKET_WORDS]) {
-    const uint4* b4 = reinterpret_cast<const uint4*>(b);
-    uint4 v[BUCKET_WORDS / 2];
-#pragma unroll
-    for (int c = 0; c < BUCKET_WORDS / 2; c++) v[c] = b4[c];
-#pragma unroll
-    for (int c = 0; c < BUCKET_WORDS / 2; c++) {
-        bw[2 * c] = ((uint64_t)v[c].y << 32) | v[c].x;
-        bw[2 * c + 1] = ((uint64_t)v[c].w << 32) | v[c].z;
-    }
-}
-
 // k_histo: hist[min(T(c), n_bins - 1)] += 1 for every occupied slot.  One sweep of the table, a
 // bucket per thread (as k_dump); the bins below HISTO_LDS_BINS are counted per workgroup in LDS
 // and flushed with one global atomic per non-zero bin, the rare larger values go straight to
@@ -161,7 +144,7 @@ __global__ __launch_bounds__(HISTO_T) void k_histo(TableView tv, int count_mode,
     for (uint64_t bkt = (uint64_t)blockIdx.x * HISTO_T + threadIdx.x; bkt < tv.nbuckets;
          bkt += (uint64_t)gridDim.x * HISTO_T) {
         uint64_t bw[BUCKET_WORDS];
-        query_load_bucket(tv.buckets + bkt * BUCKET_WORDS, bw);
+        load_bucket(tv.buckets + bkt * BUCKET_WORDS, bw);
 #pragma unroll
         for (int s = 0; s < S; s++) {
             if (bw[s * W] == EMPTY) continue;

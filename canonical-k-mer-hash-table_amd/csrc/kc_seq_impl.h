@@ -6,7 +6,7 @@
 // p, every non-ACGT byte a break).  A thread takes the run_width(W) consecutive window starts
 // s0 .. s0 + RUNW - 1, i.e. the windows ending at s0 + k - 1 ..: run_windows extracts the first
 // in O(1) and rolls the rest, each is made canonical, mixed into its table key and looked up with
-// the probe loops of kc_query_impl.h.  No key goes through HBM.  The answers are written at the
+// lookup_thread (kc_query_impl.h; the probe's rules: kc_table_read.h).  No key goes through HBM.  The answers are written at the
 // windows' start positions, RUNW consecutive uint32 per thread, so a wave's stores cover one
 // contiguous range.
 //
@@ -27,7 +27,8 @@ namespace kc {
 // calls it with its own table key (mine: it has one) and gets that key's T(c) back.  16 lanes read
 // a bucket as one 128-byte request; the wave takes 16 steps of four keys.  (k_lookup_coop keeps
 // its own copy of the loop: calling this function from it changes the register allocation of a
-// kernel whose code and measurements stay as they are.)
+// kernel whose code and measurements stay as they are.  Both walk the probe sequence of
+// kc_table_read.h and end by its invariant; table_probe there is the form of one thread per key.)
 template <int W>
 DEV uint32_t lookup_coop(const TableView& tv, const uint64_t (&t)[W], bool mine, int count_mode, int lane) {
     static_assert(W <= 2, "the group compares at most two words per slot");

@@ -1,6 +1,7 @@
 // kc_table_insert.h -- the direct insert of one table key into the full-key table in HBM, shared
 // by the counting kernels (kc_count_impl.h) and the table algebra (kc_join_impl.h).  The table's
-// layout and the READY protocol of multi-word keys are described at the top of kc_count_impl.h.
+// layout and the READY protocol of multi-word keys are described at the top of kc_count_impl.h;
+// the readers' side of the probe invariant it keeps is kc_table_read.h.
 #pragma once
 #include "kc_common.h"
 

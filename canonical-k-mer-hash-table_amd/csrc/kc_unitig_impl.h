@@ -17,7 +17,7 @@
 //   k_unitig_edges   (kc_unitig_graph* only) the edges between unitigs: every edge bit of a unitig
 //                    end, the neighbour probed for its slot and mapped to its unitig's record.
 //
-// Plain loads of the table, no atomics on it, every probe bounded by BPR; every store index is a
+// The table is only read (kc_table_read.h), every probe bounded by BPR; every store index is a
 // cursor value below `bound`, an id below the node count, or an offset k_unitig_heads bounded.
 #pragma once
 #include "kc_graph_impl.h"
@@ -36,9 +36,7 @@ DEV uint8_t unitig_base(uint64_t c) { return (uint8_t)(0x54474341u >> (8 * ((uin
 
 template <int W>
 __global__ __launch_bounds__(GRAPH_T) void k_unitig_number(UnitigArgs g) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     __shared__ uint32_t s_tc[GRAPH_RPT][GRAPH_T];  // T(c) of call r of thread t, 0: no node
-    __shared__ unsigned long long s_wt[GRAPH_T / 64], s_base;
     uint32_t mine = 0;
     uint64_t first_slot = 0;
     constexpr uint64_t step = GRAPH_BUCKET_MAP ? 1 : GRAPH_T;
@@ -47,24 +45,14 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_number(UnitigArgs g) {
         g.tv,
         [&](bool in, uint64_t slot, const uint64_t (&tk)[W], uint64_t cw, int r) {
             const uint32_t tc = tc_of(cw, g.count_mode);
-            const bool node = in && tk[0] != EMPTY && join_in_range(tc, g.lo, g.hi);
+            const bool node = in && tk[0] != EMPTY && in_range(tc, g.lo, g.hi);
             if (r == 0) first_slot = slot;
             s_tc[r][threadIdx.x] = node ? tc : 0;  // (a node's T(c) is at least lo >= 1)
             mine += node;
             if (in && !node) g.u.id_of_slot[slot] = UNITIG_NO_ID;
         },
         [&] {
-            const uint32_t incl = wave_incl_sum(mine);
-            if (lane == 63) s_wt[wid] = incl;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                unsigned long long tot = 0;
-                for (int w = 0; w < GRAPH_T / 64; w++) tot += s_wt[w];
-                s_base = tot ? atomicAdd(g.u.ctl + UC_NODES, tot) : 0;
-            }
-            __syncthreads();
-            uint64_t id = s_base + incl - mine;
-            for (int w = 0; w < wid; w++) id += s_wt[w];
+            uint64_t id = block_reserve(mine, g.u.ctl + UC_NODES);
             constexpr int RPT = GRAPH_BUCKET_MAP ? S : GRAPH_ITERS;
 #pragma unroll 1
             for (int r = 0; r < RPT && mine; r++) {
@@ -80,7 +68,7 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_number(UnitigArgs g) {
                 id++;
             }
             mine = 0;
-            __syncthreads();
+            __syncthreads();  // block_reserve's shared words are the next tile's too
         });
 }
 
@@ -92,7 +80,7 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_succ(UnitigArgs g) {
         g.tv,
         [&](bool in, uint64_t slot, const uint64_t (&tk)[W], uint64_t cw, int) {
             const uint32_t tc = tc_of(cw, g.count_mode);
-            if (!(in && tk[0] != EMPTY && join_in_range(tc, g.lo, g.hi))) return;
+            if (!(in && tk[0] != EMPTY && in_range(tc, g.lo, g.hi))) return;
             const uint32_t id = g.u.id_of_slot[slot];
             if (id >= n_nodes) return;
             uint64_t K[W], RC[W];
@@ -153,11 +141,8 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_emit(TableView tv, int k, Un
         if (slot >= n_slots) continue;
         const uint32_t p = u.pos[i], pos = p & 0x7FFFFFFFu;
         if (pos >= u.off[2 * (uint64_t)st + 1]) continue;  // (past the length the offset was bounded with)
-        const uint64_t bucket = slot / S;
-        const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS + (slot - bucket * S) * W;
         uint64_t tk[W], K[W], X[W];
-#pragma unroll
-        for (int j = 0; j < W; j++) tk[j] = bk[j];
+        slot_tkey<W>(tv, slot, tk);
         from_tkey<W>(tk, K);
         if (p >> 31) {
             revcomp<W>(K, rk, X);
@@ -197,8 +182,6 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_edges(TableView tv, int k, U
     constexpr int S = BUCKET_WORDS / (W + 1);
     const RollConst rk = make_roll<W>(k, 0, 0);
     const uint64_t n_nodes = unitig_nodes(u), n_slots = tv.nbuckets * S;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __shared__ unsigned long long s_wt[GRAPH_T / 64], s_base;
     unsigned long long dead = 0;
     const uint64_t tiles = (n_nodes + GRAPH_T - 1) / GRAPH_T;
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -209,11 +192,8 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_edges(TableView tv, int k, U
             const bool end_r = u.succ[2 * i] == UNITIG_END;
             bool end_l = u.succ[2 * i + 1] == UNITIG_END;
             if (end_l && !(k & 1)) {  // a palindrome (even k only) has no link, so both its sides end
-                const uint64_t bucket = slot / S;
-                const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS + (slot - bucket * S) * W;
                 uint64_t tk[W], K[W], RC[W];
-#pragma unroll
-                for (int j = 0; j < W; j++) tk[j] = bk[j];
+                slot_tkey<W>(tv, slot, tk);
                 from_tkey<W>(tk, K);
                 revcomp<W>(K, rk, RC);
                 if (key_eq<W>(K, RC)) end_l = false;
@@ -223,25 +203,12 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_edges(TableView tv, int k, U
             dead += (end_r && !(eb & 0x0Fu)) + (end_l && !(eb & 0xF0u));
         }
         const uint32_t mine = (uint32_t)__popc(e);
-        const uint32_t incl = wave_incl_sum(mine);
-        if (lane == 63) s_wt[wid] = incl;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long tot = 0;
-            for (int w = 0; w < GRAPH_T / 64; w++) tot += s_wt[w];
-            s_base = tot ? atomicAdd(u.ctl + UC_EDGES, tot) : 0;
-        }
-        __syncthreads();
-        uint64_t idx = s_base + incl - mine;
-        for (int w = 0; w < wid; w++) idx += s_wt[w];
+        uint64_t idx = block_reserve(mine, u.ctl + UC_EDGES);
         if (out && e && idx < cap) {
-            const uint64_t bucket = slot / S;
-            const uint64_t* bk = tv.buckets + bucket * BUCKET_WORDS + (slot - bucket * S) * W;
             uint64_t K[W], RC[W];
             {
                 uint64_t tk[W];
-#pragma unroll
-                for (int j = 0; j < W; j++) tk[j] = bk[j];
+                slot_tkey<W>(tv, slot, tk);
                 from_tkey<W>(tk, K);
             }
             revcomp<W>(K, rk, RC);
@@ -268,16 +235,11 @@ __global__ __launch_bounds__(GRAPH_T) void k_unitig_edges(TableView tv, int k, U
                 out[idx] = make_uint4(from, to, from_rev | to_rev << 1, 0);  // KC_EDGE_FROM_REV, KC_EDGE_TO_REV
             }
         }
-        __syncthreads();  // s_wt and s_base are the next tile's too
+        __syncthreads();  // block_reserve's shared words are the next tile's too
     }
-    for (int m = 32; m >= 1; m >>= 1) dead += __shfl_xor(dead, m, 64);
-    if (lane == 0) s_wt[wid] = dead;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tot = 0;
-        for (int w = 0; w < GRAPH_T / 64; w++) tot += s_wt[w];
-        if (tot) atomicAdd(u.ctl + UC_DEAD, tot);
-    }
+    const unsigned long long v[1] = {dead};
+    unsigned long long* const dst[1] = {u.ctl + UC_DEAD};
+    block_sum_add<1>(v, dst);
 }
 
 template <int W>
