@@ -16,7 +16,7 @@ static_assert(sizeof(kc_cdbg_stats) == (UC_CDBG_ZERO + 1 - UC_STATS) * sizeof(un
 static_assert(KC_EDGE_FROM_REV == 1 && KC_EDGE_TO_REV == 2, "k_unitig_edges writes from_rev | to_rev << 1");
 static_assert(sizeof(UnitigState) * 4 + 4 + 8 + 8 + 4 + 4 + 16 == UNITIG_NODE_BYTES, "kc_unitig_host.h counts a node's bytes");
 
-static int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count) {
+int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count) {
     if (c->cfg.k < 2) return c->fail(KC_ERR_ARG, "unitigs need k >= 2");
     if (max_count && min_count > max_count) return c->fail(KC_ERR_ARG, "kc_unitigs: min_count is above max_count");
     JOB_OK(c);
@@ -24,8 +24,8 @@ static int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count) {
     return KC_OK;
 }
 
-UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound) {
-    const UnitigLayout l = unitig_layout(bound);
+UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound, bool with_verdict) {
+    const UnitigLayout l = unitig_layout(bound, with_verdict);
     uint64_t* b = c->d_unitig_node;
     UnitigBufs u{};
     u.edges = c->d_graph_edges;
@@ -40,28 +40,30 @@ UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound) {
     u.start = reinterpret_cast<uint32_t*>(b + l.start);
     u.pos = reinterpret_cast<uint32_t*>(b + l.pos);
     u.ctl = c->d_unitig_ctl;
+    u.verdict = with_verdict ? reinterpret_cast<uint8_t*>(b + l.verdict) : nullptr;
     return u;
 }
 
 // The ranking on s for up to `bound` nodes (the caller has joined s): the scratch first -- a failure
 // is reported before any kernel of the call is launched -- then the three sweeps and the jump
-// launches.  Leaves the views and the rounds for unitig_write.
-static int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u,
-                       int* rounds, bool with_rec = false) {
+// launches.  Leaves the views and the rounds for unitig_write.  with_rec: the record indices of
+// kc_unitig_graph*; with_verdict: the verdict bytes of kc_clean* (kc_api_clean.cpp).
+int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u,
+                int* rounds, bool with_rec, bool with_verdict) {
     const uint64_t slots = c->nbuckets * (uint64_t)c->S;
     bound = std::max<uint64_t>(1, std::min(bound, slots));
     if (bound >= UNITIG_MAX_BOUND)
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: " + std::to_string(bound) + " node ids do not fit 32-bit states (the "
                                      "device form sizes by the table's slots, kc_unitigs by the k-mers from min_count on)");
-    const uint64_t words = unitig_layout(bound).words;
+    const uint64_t words = unitig_layout(bound, with_verdict).words;
     if (c->d_graph_edges.capacity() < slots || c->d_unitig_ids.capacity() < slots || c->d_unitig_node.capacity() < words ||
         (with_rec && c->d_unitig_rec.capacity() < bound))
-        make_room(c, unitig_scratch_bytes(slots, bound, with_rec));
+        make_room(c, unitig_scratch_bytes(slots, bound, with_rec, with_verdict));
     if (!c->d_graph_edges.reserve(slots) || !c->d_unitig_ids.reserve(slots) || !c->d_unitig_node.reserve(words) ||
         !c->d_unitig_ctl.reserve(UNITIG_CTL_WORDS) || (with_rec && !c->d_unitig_rec.reserve(bound)))
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: scratch allocation failed (" +
-                                     std::to_string(unitig_scratch_bytes(slots, bound, with_rec)) + " bytes)");
-    *u = unitig_bufs(c, bound);
+                                     std::to_string(unitig_scratch_bytes(slots, bound, with_rec, with_verdict)) + " bytes)");
+    *u = unitig_bufs(c, bound, with_verdict);
     *rounds = unitig_rounds(bound);
     HIPCHK(c, hipMemsetAsync(u->ctl, 0, UNITIG_CTL_WORDS * sizeof(unsigned long long), s));
     HIPCHK(c, launch_unitig_succ(table_view(c), c->cfg.k, c->cfg.mode == 0 ? 0 : 1, min_count ? min_count : 1, max_count,
@@ -83,7 +85,7 @@ static int unitig_write(kc_ctx* c, const UnitigBufs& u, int rounds, kc_unitig* r
 
 // the ids' bound of the host forms: the k-mers with T(c) >= min_count (one count-only sweep, as
 // kc_graph's); waits
-static int unitig_bound(kc_ctx* c, uint32_t min_count, unsigned long long* bound) {
+int unitig_bound(kc_ctx* c, uint32_t min_count, unsigned long long* bound) {
     hipStream_t s = c->stream;
     int rc = sync_for_read(c);
     if (rc) return rc;

@@ -36,7 +36,7 @@
 
 namespace {
 
-enum CliExit { kConversion = 104, kValidation = 105, kRequired = 106, kRequires = 107, kExtras = 109 };
+enum CliExit { kConversion = 104, kValidation = 105, kRequired = 106, kRequires = 107, kExcludes = 108, kExtras = 109 };
 
 struct Args {
     std::string input, output;
@@ -96,6 +96,15 @@ struct Args {
     std::string gfa;
     unsigned long long gfa_min = 0, gfa_max = 0;
     bool gfa_min_set = false, gfa_max_set = false;
+    // --clean-tips N / --clean-isolated N [--clean-max-mean M] [--clean-rounds R] [--clean-min N]
+    // [--clean-max N] [--clean-out FILE] [--clean-stats FILE]: graph cleaning (kc_clean) of the counted
+    // table into a new one, R rounds at the most, which --graph, --unitigs and --gfa then read (their
+    // own ranges applied to it); every other output still reads the counted table.  The range as for
+    // --graph.
+    unsigned long long clean_tips = 0, clean_iso = 0, clean_max_mean = 0, clean_rounds = 1, clean_min = 0, clean_max = 0;
+    bool clean_tips_set = false, clean_iso_set = false, clean_dep_set = false, clean_min_set = false;
+    std::string clean_out, clean_stats;
+    bool cleaning() const { return clean_tips_set || clean_iso_set; }
 };
 
 const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
@@ -153,7 +162,18 @@ void usage(const char* prog) {
                  "                              between unitigs \"L <i> <+|-> <j> <+|-> <k-1>M\", and the two links\n"
                  "                              \"L i + i +\", \"L i - i -\" that close a circular unitig\n"
                  "  --gfa-min,--gfa-max UINT    a k-mer is a node when its count is in this range (def. the -a value and\n"
-                 "                              up); needs --gfa\n\n"
+                 "                              up); needs --gfa\n"
+                 "  --clean-tips UINT           clean the graph first: remove the dead-end branches (tips) of at most this\n"
+                 "                              many k-mers (k - 1 is customary; 0 keeps them); --graph, --unitigs and\n"
+                 "                              --gfa then read the cleaned table, every other output the counted one\n"
+                 "  --clean-isolated UINT       ... and the unitigs connected to nothing of at most this many k-mers\n"
+                 "  --clean-max-mean UINT       never remove a unitig whose mean count is above this (def. no guard)\n"
+                 "  --clean-rounds UINT         cleaning rounds, each on the result of the one before; they stop early\n"
+                 "                              after a round that removes nothing (def. 1)\n"
+                 "  --clean-min,--clean-max UINT\n"
+                 "                              a k-mer is a node when its count is in this range (def. the -a value and up)\n"
+                 "  --clean-out FILE            write every k-mer of the cleaned table, as -o writes the counted one's\n"
+                 "  --clean-stats FILE          a line of \"<name> <value>\" pairs per round\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -369,6 +389,25 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 (o == "--gfa-min" ? a->gfa_min : a->gfa_max) = u;
                 (o == "--gfa-min" ? a->gfa_min_set : a->gfa_max_set) = true;
+            } else if (o == "--clean-tips" || o == "--clean-isolated" || o == "--clean-max-mean" || o == "--clean-rounds" ||
+                       o == "--clean-min" || o == "--clean-max") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                if (o == "--clean-tips") {
+                    a->clean_tips = u;
+                    a->clean_tips_set = true;
+                } else if (o == "--clean-isolated") {
+                    a->clean_iso = u;
+                    a->clean_iso_set = true;
+                } else {
+                    (o == "--clean-max-mean" ? a->clean_max_mean : o == "--clean-rounds" ? a->clean_rounds
+                     : o == "--clean-min"    ? a->clean_min : a->clean_max) = u;
+                    a->clean_dep_set = true;
+                    if (o == "--clean-min") a->clean_min_set = true;
+                }
+            } else if (o == "--clean-out" || o == "--clean-stats") {
+                (o == "--clean-out" ? a->clean_out : a->clean_stats) = v;
+                a->clean_dep_set = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -433,6 +472,14 @@ int parse(int argc, char** argv, Args* a) {
         return cli_error(kRequires, "--gfa-min/--gfa-max require --gfa");
     if (!a->gfa_min_set) a->gfa_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
     if (a->gfa_max && a->gfa_min > a->gfa_max) return cli_error(kValidation, "--gfa-min: a minimum above its maximum");
+    if (a->clean_dep_set && !a->cleaning())
+        return cli_error(kRequires, "--clean-max-mean/--clean-rounds/--clean-min/--clean-max/--clean-out/--clean-stats "
+                                    "require --clean-tips or --clean-isolated");
+    if (!a->clean_min_set) a->clean_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if (a->clean_max && a->clean_min > a->clean_max)
+        return cli_error(kValidation, "--clean-min: a minimum above its maximum");
+    if (a->clean_rounds < 1) return cli_error(kValidation, "--clean-rounds: Value 0 not in range 1 to inf");
+    if (a->cleaning() && !a->op_name.empty()) return cli_error(kExcludes, "--clean-tips/--clean-isolated exclude --op");
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -1288,18 +1335,82 @@ int main(int argc, char** argv) {
         std::cout << "Corrected " << bases << " bases in " << recs << " of " << nrec << " records (" << cands
                   << " candidates, " << ambig << " ambiguous, " << dropped << " dropped)\n";
     }
-    if (!a.graph.empty() || !a.graph_stats.empty()) {  // extension: the de Bruijn graph of the counted k-mers
+    // --clean-tips / --clean-isolated (extension): up to --clean-rounds rounds of graph cleaning, each
+    // into a new table sized from a statistics-only call -- no Bloom filter, every k-mer of it output
+    // (-a 1) -- which the three graph outputs below read instead of the counted table
+    kc_ctx* gctx = ctx;
+    auto gdie = [&](const char* what) {
+        std::cerr << what << ": " << kc_last_error(gctx) << std::endl;
+        if (gctx != ctx) kc_destroy(gctx);
+        kc_destroy(ctx);
+        std::exit(1);
+    };
+    if (a.cleaning()) {
+        FILE* sf = nullptr;
+        if (!a.clean_stats.empty() && !(sf = std::fopen(a.clean_stats.c_str(), "w"))) {
+            std::cerr << "cannot write " << a.clean_stats << std::endl;
+            kc_destroy(ctx);
+            return 1;
+        }
+        kc_clean_desc cd;
+        std::memset(&cd, 0, sizeof cd);
+        cd.min_count = (uint32_t)a.clean_min;
+        cd.max_count = (uint32_t)a.clean_max;
+        cd.tip_max_nodes = (uint32_t)a.clean_tips;
+        cd.iso_max_nodes = (uint32_t)a.clean_iso;
+        cd.max_mean = (uint32_t)a.clean_max_mean;
+        for (unsigned long long round = 1; round <= a.clean_rounds; round++) {
+            kc_clean_stats cs;
+            if (kc_clean(nullptr, gctx, &cd, &cs) != KC_OK) gdie("graph cleaning");
+            kc_config rcfg = cfg;
+            rcfg.bf_enable = 0;
+            rcfg.est_unique = 0;
+            rcfg.min_abundance = 1;
+            rcfg.table_slots = cs.out_keys + cs.out_keys / 8 + 4096;
+            rcfg.batch_bytes = 1 << 20;  // (nothing is staged into it)
+            kc_ctx* next = nullptr;
+            if (kc_create(&rcfg, &next) != KC_OK) {
+                std::cerr << "kc_create (graph cleaning): " << kc_last_error(nullptr) << std::endl;
+                if (gctx != ctx) kc_destroy(gctx);
+                kc_destroy(ctx);
+                return 1;
+            }
+            kc_stats str;
+            if (kc_clean(next, gctx, &cd, &cs) != KC_OK || kc_finish(next, &str) != KC_OK) {
+                std::cerr << "graph cleaning: " << kc_last_error(next) << std::endl;
+                kc_destroy(next);
+                if (gctx != ctx) kc_destroy(gctx);
+                kc_destroy(ctx);
+                return 1;
+            }
+            if (gctx != ctx) kc_destroy(gctx);
+            gctx = next;
+            if (sf)
+                std::fprintf(sf, "round %llu unitigs %llu nodes %llu tips %llu tip_nodes %llu isolated %llu isolated_nodes %llu "
+                                 "out_keys %llu out_sum %llu\n", round, (unsigned long long)cs.unitigs,
+                             (unsigned long long)cs.nodes, (unsigned long long)cs.tips, (unsigned long long)cs.tip_nodes,
+                             (unsigned long long)cs.isolated, (unsigned long long)cs.isolated_nodes,
+                             (unsigned long long)cs.out_keys, (unsigned long long)cs.out_sum);
+            std::cout << "Graph cleaning round " << round << ": " << cs.unitigs << " unitigs, " << cs.nodes << " nodes; removed "
+                      << cs.tips << " tips (" << cs.tip_nodes << " nodes) and " << cs.isolated << " isolated unitigs ("
+                      << cs.isolated_nodes << " nodes); kept " << cs.out_keys << " k-mers in " << str.table_slots << " slots\n";
+            if (!cs.tips && !cs.isolated) break;
+        }
+        if (sf && std::fclose(sf) != 0) { std::cerr << "cannot write " << a.clean_stats << std::endl; gdie("graph cleaning"); }
+        if (!a.clean_out.empty() && kc_write(gctx, a.clean_out.c_str()) != KC_OK) gdie("writing the cleaned k-mers");
+    }
+    if (!a.graph.empty() || !a.graph_stats.empty()) {  // extension: the de Bruijn graph of the counted (or cleaned) k-mers
         uint64_t* grec = nullptr;
         uint64_t gn = 0;
         kc_graph_stats gst;
         const bool lines = !a.graph.empty();
-        if (kc_graph(ctx, (uint32_t)a.graph_min, (uint32_t)a.graph_max, lines ? &grec : nullptr, lines ? &gn : nullptr,
+        if (kc_graph(gctx, (uint32_t)a.graph_min, (uint32_t)a.graph_max, lines ? &grec : nullptr, lines ? &gn : nullptr,
                      &gst) != KC_OK)
-            die("de Bruijn graph");
+            gdie("de Bruijn graph");
         if (lines) {
             FILE* f = std::fopen(a.graph.c_str(), "w");
             if (!f) { std::cerr << "cannot write " << a.graph << std::endl; kc_free(grec); kc_destroy(ctx); return 1; }
-            const int W = kc_key_words(ctx), k = (int)a.k;
+            const int W = kc_key_words(gctx), k = (int)a.k;
             std::string line((size_t)k, 'A');
             for (uint64_t i = 0; i < gn; i++) {
                 const uint64_t* r = grec + i * (W + 1);
@@ -1339,7 +1450,7 @@ int main(int argc, char** argv) {
         kc_unitig* urec = nullptr;
         uint8_t* ubases = nullptr;
         kc_unitig_stats ust;
-        if (kc_unitigs(ctx, (uint32_t)a.unitigs_min, (uint32_t)a.unitigs_max, &urec, &ubases, &ust) != KC_OK) die("unitigs");
+        if (kc_unitigs(gctx, (uint32_t)a.unitigs_min, (uint32_t)a.unitigs_max, &urec, &ubases, &ust) != KC_OK) gdie("unitigs");
         FILE* f = std::fopen(a.unitigs.c_str(), "w");
         if (!f) { std::cerr << "cannot write " << a.unitigs << std::endl; kc_free(urec); kc_free(ubases); kc_destroy(ctx); return 1; }
         char head[160];
@@ -1362,7 +1473,7 @@ int main(int argc, char** argv) {
         uint8_t* ubases = nullptr;
         kc_unitig_edge* uedges = nullptr;
         kc_cdbg_stats cst;
-        if (kc_unitig_graph(ctx, (uint32_t)a.gfa_min, (uint32_t)a.gfa_max, &urec, &ubases, &uedges, &cst) != KC_OK) die("gfa");
+        if (kc_unitig_graph(gctx, (uint32_t)a.gfa_min, (uint32_t)a.gfa_max, &urec, &ubases, &uedges, &cst) != KC_OK) gdie("gfa");
         FILE* f = std::fopen(a.gfa.c_str(), "w");
         if (!f) {
             std::cerr << "cannot write " << a.gfa << std::endl;
@@ -1406,7 +1517,7 @@ int main(int argc, char** argv) {
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
     if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty() || !a.graph.empty() ||
-        !a.graph_stats.empty() || !a.unitigs.empty() || !a.gfa.empty())
+        !a.graph_stats.empty() || !a.unitigs.empty() || !a.gfa.empty() || a.cleaning())
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
                   << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")
@@ -1416,6 +1527,7 @@ int main(int argc, char** argv) {
     std::cout << "Device table capacity: " << stt.table_slots << " slots\n";
     std::cout << "Input path: " << (d_img ? "device image" : "host chunks")
               << (stt.reused_passes ? " (counting pass from the Bloom pass's partitions)" : "") << "\n";
+    if (gctx != ctx) kc_destroy(gctx);
     kc_destroy(ctx);
     up.release();
     up.free_image();

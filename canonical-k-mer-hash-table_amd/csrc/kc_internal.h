@@ -538,6 +538,7 @@ struct UnitigBufs {
     uint32_t* pos;         // [id] its position | read on the reverse strand << 31
     uint64_t* off;         // [2 start id] the unitig's base offset, UNITIG_NO_OFF: its bases do not fit; [+ 1] its nodes
     unsigned long long* ctl;  // UNITIG_CTL_WORDS
+    uint8_t* verdict;      // [start id] CLEAN_KEEP / CLEAN_TIP / CLEAN_ISOLATED (kc_clean* only, else nullptr)
 };
 // the nodes the sweep numbered, never more than the ids that fit
 __device__ inline uint64_t unitig_nodes(const UnitigBufs& u) {
@@ -566,9 +567,32 @@ hipError_t launch_unitig_rank(UnitigBufs u, int rounds, hipStream_t s);
 hipError_t launch_unitig_heads(UnitigBufs u, int k, int rounds, void* records, uint64_t cap_unitigs, uint64_t cap_bases,
                                uint32_t* rec, hipStream_t s);
 
+// Graph cleaning (include/kc_api.h kc_clean_device), after a ranking and launch_unitig_heads of the
+// same UnitigBufs.  The verdict (kc_unitig.hip, no key): the node at position 0 of every unitig
+// classifies it from its two end states, the ends' successors and edge nibbles, and writes one of
+// the values below at verdict[its id]; stats (nullptr: none) receives the first six words of
+// kc_clean_stats, added to.  The copy (kc_clean_impl.h): every node of a kept unitig reads its slot's
+// key and count word in src and adds the raw count into dst (dst.buckets == nullptr: nothing is
+// inserted); stats + 6 and + 7 receive out_keys and out_sum, ctr (dst's, nullptr without dst)
+// inserted += the counts added and overflow += the inserts that found their region full.
+constexpr uint8_t CLEAN_KEEP = 0, CLEAN_TIP = 1, CLEAN_ISOLATED = 2;
+struct CleanRule {
+    uint32_t tip_max_nodes, iso_max_nodes, max_mean;  // kc_clean_desc's, 0: off
+};
+// zeroes the verdict bytes first; n_slots: src's table slots (the bound of slot_of's values)
+hipError_t launch_unitig_verdict(UnitigBufs u, int rounds, uint64_t n_slots, CleanRule rule, unsigned long long* stats,
+                                 hipStream_t s);
+template <int W>
+struct CleanOps {
+    static hipError_t copy(TableView src, TableView dst, UnitigBufs u, DevCounters* ctr, unsigned long long* stats,
+                           hipStream_t s);
+};
+hipError_t launch_clean(TableView src, TableView dst, UnitigBufs u, DevCounters* ctr, unsigned long long* stats,
+                        hipStream_t s);
+
 // Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip, kc_unitig.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
-// JoinOps, GraphOps, UnitigOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// JoinOps, GraphOps, UnitigOps, CleanOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_clean_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

@@ -49,6 +49,14 @@ DEV void slot_tkey(const TableView& tv, uint64_t slot, uint64_t (&tk)[W]) {
     for (int i = 0; i < W; i++) tk[i] = key[i];
 }
 
+// the count word of that slot (CNT_MASK takes the READY flag off)
+template <int W>
+DEV uint64_t slot_count_word(const TableView& tv, uint64_t slot) {
+    constexpr int S = BUCKET_WORDS / (W + 1);
+    const uint64_t bucket = slot / S;
+    return tv.buckets[bucket * BUCKET_WORDS + S * W + (slot - bucket * S)];
+}
+
 // The probe of table key t, one thread per key: S strided loads of key word 0 per bucket, the other
 // words only where word 0 matches.  hit(bucket, bk, sl) is called at the matching slot -- bucket its
 // index, bk its words, sl the slot in it, whose count word is bk[S * W + sl] -- and its value

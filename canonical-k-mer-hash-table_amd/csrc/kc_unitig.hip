@@ -26,12 +26,21 @@
 //                   index and a base offset (two atomics per workgroup and tile), writes the record
 //                   if it fits and leaves the offset, bounded by cap_bases, at off[2 start], and,
 //                   for the edges between unitigs (k_unitig_edges), the record index at rec[start].
+//   k_unitig_verdict  (kc_clean* only, after the heads) the node at position 0 again, with n and
+//                   count_sum from its two states as above and the two end states a and b themselves:
+//                   the unitig is open when succ of both is UNITIG_END (a cut circle's ends have
+//                   successors), the degree of an end is the popcount of the nibble of its exit side
+//                   in its node's edge byte, and the rule of include/kc_api.h kc_clean_device gives
+//                   the verdict byte at its id.  Coalesced: the states, pos; scattered, twice per
+//                   unitig: succ, slot_of and the edge byte of an end.
+#include "kc_block.h"
 #include "kc_common.h"
 #include "kc_internal.h"
 
 namespace kc {
 
 constexpr int UT = 256;
+static_assert(UT == BLOCK_T, "k_unitig_verdict reduces with block_sum_add");
 constexpr uint64_t UNITIG_BLOCKS = 8192;
 
 // phase 0: the first ranking, a path has at most 2 * nodes states; phase 1: the cut circles
@@ -232,6 +241,53 @@ __global__ __launch_bounds__(UT) void k_unitig_heads(UnitigBufs u, int k, int j,
     }
 }
 
+// the degree of the unitig end at state x (< 2 * nodes): the edge nibble of its node at its exit side
+DEV uint32_t unitig_end_degree(const UnitigBufs& u, uint32_t x, uint64_t n_slots) {
+    const uint64_t slot = u.slot_of[x >> 1];
+    if (slot >= n_slots) return 1;  // (cannot be: it then counts as connected, and nothing is removed for it)
+    return (uint32_t)__popc(((uint32_t)u.edges[slot] >> (4 * (x & 1))) & 15);
+}
+
+__global__ __launch_bounds__(UT) void k_unitig_verdict(UnitigBufs u, int j, uint64_t n_slots, CleanRule rule,
+                                                       unsigned long long* __restrict__ stats) {
+    const uint64_t n_nodes = unitig_nodes(u), n_states = 2 * n_nodes;
+    const UnitigState* __restrict__ F = u.st[u.ctl[UC_SRC + j] & 1];
+    unsigned long long n_unitigs = 0, n_mine = 0, n_tips = 0, n_tip_nodes = 0, n_iso = 0, n_iso_nodes = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * UT + threadIdx.x; i < n_nodes; i += (uint64_t)gridDim.x * UT) {
+        n_mine++;
+        const UnitigState r = F[2 * i], l = F[2 * i + 1];
+        uint32_t a = r.nxt & ~UNITIG_DONE, b = l.nxt & ~UNITIG_DONE, dR = r.dist, dL = l.dist;
+        uint64_t sR = r.sum, sL = l.sum;
+        // (as k_unitig_heads: a state that is not DONE stands alone)
+        if (!(r.nxt & UNITIG_DONE) || a >= n_states) a = (uint32_t)(2 * i), dR = 0, sR = 0;
+        if (!(l.nxt & UNITIG_DONE) || b >= n_states) b = (uint32_t)(2 * i + 1), dL = 0, sL = 0;
+        const bool fwd = (b >> 1) <= (a >> 1);
+        if ((fwd ? dL : dR) != 0) continue;  // not at position 0
+        const uint64_t n = (uint64_t)dR + dL + 1, sum = sR + sL + u.tc[i];
+        n_unitigs++;
+        uint8_t v = CLEAN_KEEP;
+        if (u.succ[a] == UNITIG_END && u.succ[b] == UNITIG_END) {  // open
+            const bool dead_a = unitig_end_degree(u, a, n_slots) == 0, dead_b = unitig_end_degree(u, b, n_slots) == 0;
+            const bool guard = !rule.max_mean || sum <= (uint64_t)rule.max_mean * n;
+            if (dead_a && dead_b) {
+                if (rule.iso_max_nodes && n <= rule.iso_max_nodes && guard) v = CLEAN_ISOLATED;
+            } else if (dead_a || dead_b) {
+                if (rule.tip_max_nodes && n <= rule.tip_max_nodes && guard) v = CLEAN_TIP;
+            }
+        }
+        u.verdict[i] = v;
+        n_tips += v == CLEAN_TIP;
+        n_tip_nodes += v == CLEAN_TIP ? n : 0;
+        n_iso += v == CLEAN_ISOLATED;
+        n_iso_nodes += v == CLEAN_ISOLATED ? n : 0;
+    }
+    // kc_clean_stats' first six words
+    const unsigned long long v[6] = {n_unitigs, n_mine, n_tips, n_tip_nodes, n_iso, n_iso_nodes};
+    unsigned long long* const dst[6] = {stats, stats ? stats + 1 : nullptr, stats ? stats + 2 : nullptr,
+                                        stats ? stats + 3 : nullptr, stats ? stats + 4 : nullptr, stats ? stats + 5 : nullptr};
+    block_sum_add<6>(v, dst);
+}
+
 static unsigned unitig_grid(uint64_t items) {
     const uint64_t need = (items + UT - 1) / UT;
     return (unsigned)(need < UNITIG_BLOCKS ? (need ? need : 1) : UNITIG_BLOCKS);
@@ -263,6 +319,15 @@ hipError_t launch_unitig_heads(UnitigBufs u, int k, int rounds, void* records, u
     return hipGetLastError();
 }
 
+hipError_t launch_unitig_verdict(UnitigBufs u, int rounds, uint64_t n_slots, CleanRule rule, unsigned long long* stats,
+                                 hipStream_t s) {
+    if (!u.verdict) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(u.verdict, CLEAN_KEEP, u.bound, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_unitig_verdict, dim3(unitig_grid(u.bound)), dim3(UT), 0, s, u, 2 * rounds, n_slots, rule, stats);
+    return hipGetLastError();
+}
+
 // W-dispatch of the sweeps and the bases (kc_unitig_w.hip, one translation unit per key width)
 hipError_t launch_unitig_succ(TableView t, int k, int count_mode, uint32_t lo, uint32_t hi, UnitigBufs u, hipStream_t s) {
     KC_DISPATCH(UnitigOps, t.W, succ(t, k, count_mode, lo, hi, u, s));
@@ -274,6 +339,11 @@ hipError_t launch_unitig_edges(TableView t, int k, UnitigBufs u, const uint32_t*
     const hipError_t e = hipMemsetAsync(u.ctl + UC_EDGES, 0, (UC_CDBG_ZERO + 1 - UC_EDGES) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     KC_DISPATCH(UnitigOps, t.W, edges(t, k, u, rec, out, cap, s));
+}
+// ... and of the graph cleaning's copy (kc_clean_w.hip)
+hipError_t launch_clean(TableView src, TableView dst, UnitigBufs u, DevCounters* ctr, unsigned long long* stats,
+                        hipStream_t s) {
+    KC_DISPATCH(CleanOps, src.W, copy(src, dst, u, ctr, stats, s));
 }
 
 }  // namespace kc

@@ -15,6 +15,7 @@ streams and ``torch.distributed``.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 from dataclasses import dataclass
 from typing import Iterable, List, Optional, Sequence, Tuple
@@ -66,6 +67,7 @@ EXPORTS = (
     "kc_neighbors_device", "kc_neighbors", "kc_graph_device", "kc_graph",
     "kc_unitigs_device", "kc_unitigs",
     "kc_unitig_graph_device", "kc_unitig_graph",
+    "kc_clean_device", "kc_clean",
 )
 # kc_graph* node flags (KC_GRAPH_*): bits 0-7 the edges -- bit y: canon(c[1:] + y) is a node (side
 # R), bit 4 + y: canon(y + c[:-1]) is a node (side L) -- then the two unitig links and the node bit
@@ -197,6 +199,22 @@ class kc_cdbg_stats(ctypes.Structure):  # 64 bytes
         return {n: int(getattr(self, n)) for n, _ in self._fields_[:7]}
 
 
+class kc_clean_desc(ctypes.Structure):  # 24 bytes
+    _fields_ = [(n, ctypes.c_uint32) for n in ("min_count", "max_count", "tip_max_nodes", "iso_max_nodes", "max_mean",
+                                               "reserved")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_clean_stats(ctypes.Structure):  # 64 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("unitigs", "nodes", "tips", "tip_nodes", "isolated", "isolated_nodes",
+                                               "out_keys", "out_sum")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class kc_correct_stat(ctypes.Structure):  # 16 bytes
     _fields_ = [(n, ctypes.c_uint32) for n in ("candidates", "corrected", "ambiguous", "dropped")]
 
@@ -314,6 +332,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_unitigs_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, P]),
         "kc_unitigs": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
                              ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(kc_unitig_stats)]),
+        "kc_clean_device": (I32, [P, P, ctypes.POINTER(kc_clean_desc), P, P]),
+        "kc_clean": (I32, [P, P, ctypes.POINTER(kc_clean_desc), ctypes.POINTER(kc_clean_stats)]),
         "kc_unitig_graph_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, U64, P, P]),
         "kc_unitig_graph": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
                                   ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
@@ -985,6 +1005,27 @@ class KmerCounter:
                   "kc_unitig_graph")
         return st.as_dict()
 
+    # -- graph cleaning (kc_clean*): this counter is the destination
+    def clean_device(self, src: "KmerCounter", min_count: int = 1, max_count: int = 0, tip_max_nodes: int = 0,
+                     iso_max_nodes: int = 0, max_mean: int = 0, stats_ptr: int = 0, stream: int = 0):
+        """self += the graph of src's k-mers with min_count <= T(c) <= max_count without its tips of at
+        most tip_max_nodes nodes and its isolated unitigs of at most iso_max_nodes nodes (0: the rule
+        is off; k - 1 is customary), none removed whose mean T(c) is above max_mean (0: no guard);
+        raw counts, all in HBM.  stats_ptr: 64 bytes of device memory for the kc_clean_stats (0:
+        none); enqueued on `stream`, no wait."""
+        d = _clean_desc(min_count, max_count, tip_max_nodes, iso_max_nodes, max_mean)
+        self._chk(self.lib.kc_clean_device(self._ctx, src._ctx, ctypes.byref(d), ctypes.c_void_p(stats_ptr or None),
+                                           ctypes.c_void_p(stream or None)), "kc_clean_device")
+
+    def clean(self, src: "KmerCounter", min_count: int = 1, max_count: int = 0, tip_max_nodes: int = 0,
+              iso_max_nodes: int = 0, max_mean: int = 0) -> dict:
+        """clean_device that waits; returns the statistics: unitigs and nodes of the range's graph,
+        tips, tip_nodes, isolated and isolated_nodes (what was removed), out_keys and out_sum (the
+        kept nodes and their raw counts, added here)."""
+        d, st = _clean_desc(min_count, max_count, tip_max_nodes, iso_max_nodes, max_mean), kc_clean_stats()
+        self._chk(self.lib.kc_clean(self._ctx, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_clean")
+        return st.as_dict()
+
     def compact_read(self, info: dict):
         """(slot words, secondary-array words) as uint64 arrays."""
         W = self.lib.kc_key_words(self._ctx)
@@ -1025,6 +1066,51 @@ def table_compare(a: KmerCounter, b: KmerCounter, a_range=(1, 0), b_range=(1, 0)
     r["jaccard"] = r["both"] / union if union else 0.0
     r["containment"] = r["both"] / r["a_keys"] if r["a_keys"] else 0.0
     return r
+
+
+def _clean_desc(min_count, max_count, tip_max_nodes, iso_max_nodes, max_mean) -> kc_clean_desc:
+    return kc_clean_desc(int(min_count), int(max_count), int(tip_max_nodes), int(iso_max_nodes), int(max_mean), 0)
+
+
+def clean_stats(src: KmerCounter, min_count: int = 1, max_count: int = 0, tip_max_nodes: int = 0, iso_max_nodes: int = 0,
+                max_mean: int = 0) -> dict:
+    """The statistics of KmerCounter.clean without a destination (kc_clean with dst NULL): nothing is
+    inserted anywhere, and out_keys sizes a destination."""
+    d, st = _clean_desc(min_count, max_count, tip_max_nodes, iso_max_nodes, max_mean), kc_clean_stats()
+    src._chk(src.lib.kc_clean(None, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_clean")
+    return st.as_dict()
+
+
+def clean_rounds(src: KmerCounter, rounds: int, **rule) -> Tuple[KmerCounter, List[dict]]:
+    """Up to `rounds` rounds of graph cleaning, each on the result of the one before (removing tips
+    makes longer unitigs and sometimes new tips): (the last round's table, the statistics of every
+    round run).  rule: clean()'s keywords, the same in every round.  A round first asks for the
+    statistics alone, creates a table of out_keys + out_keys / 8 + 4096 slots (src's k, mode,
+    min_abundance and device; no Bloom filter, a 1 MiB stage: it is read, not counted into) and
+    cleans into it; the intermediate table before it is closed (src never is).
+    The rounds stop early after one that removes nothing.  The caller closes the result."""
+    if rounds < 1:
+        raise ValueError("clean_rounds: rounds must be at least 1")
+    cur, stats = src, []
+    for _ in range(rounds):
+        n = clean_stats(cur, **rule)["out_keys"]
+        dst = KmerCounter(dataclasses.replace(src.cfg, table_slots=n + n // 8 + 4096, bf_enable=False, est_unique=0,
+                                              batch_bytes=1 << 20))
+        try:
+            st = dst.clean(cur, **rule)
+            dst.finish()
+        except Exception:
+            dst.close()
+            if cur is not src:
+                cur.close()
+            raise
+        if cur is not src:
+            cur.close()
+        cur = dst
+        stats.append(st)
+        if st["tips"] == 0 and st["isolated"] == 0:
+            break
+    return cur, stats
 
 
 def digest_dict(lines: int, count_sum: int, hash_sum: int, hash_xor: int) -> dict:

@@ -37,6 +37,11 @@ int main() {
     CHECK(unitig_scratch_bytes(1 << 20, 1000, true) == 5ULL * (1 << 20) + 144 * 1000);
     CHECK(unitig_scratch_bytes(268435456ULL, 268435456ULL, true) == 149 * 268435456ULL);
     CHECK(unitig_scratch_bytes(1, ~0ULL / 144 + 1, true) == 0 && unitig_scratch_bytes(1, ~0ULL / 144 + 1) != 0);
+    // ... of kc_clean*: the verdict byte per id on top
+    CHECK(unitig_scratch_bytes(1 << 20, 1000, false, true) == 5ULL * (1 << 20) + 141 * 1000);
+    CHECK(unitig_scratch_bytes(268435456ULL, 268435456ULL, false, true) == 146 * 268435456ULL);
+    CHECK(unitig_scratch_bytes(1, ~0ULL / 141 + 1, false, true) == 0 && unitig_scratch_bytes(1, ~0ULL / 141 + 1) != 0);
+    CHECK(unitig_scratch_bytes(1 << 20, 1000, true, true) == 5ULL * (1 << 20) + 145 * 1000);
     // the layout: disjoint arrays, in order, inside `words`, and within the bytes the header states
     for (uint64_t b : std::vector<uint64_t>{1, 2, 3, 1000, 86000001, UNITIG_MAX_BOUND - 1}) {
         const UnitigLayout l = unitig_layout(b);
@@ -44,6 +49,13 @@ int main() {
         CHECK(l.st0 == 0 && l.st1 - l.st0 == 6 * b && l.slot_of - l.st1 == 6 * b && l.off - l.slot_of == b);
         CHECK(l.succ - l.off == 2 * b && l.tc - l.succ == b && l.start - l.tc == half && l.pos - l.start == half);
         CHECK(l.words - l.pos == half && l.words * 8 <= UNITIG_NODE_BYTES * b + 24);
+        CHECK(l.verdict == l.words);  // (no verdict bytes unless asked for)
+        // with the verdict bytes: every earlier offset as it was, the bytes behind pos, inside the bytes stated
+        const UnitigLayout v = unitig_layout(b, true);
+        CHECK(v.st0 == l.st0 && v.st1 == l.st1 && v.slot_of == l.slot_of && v.off == l.off && v.succ == l.succ);
+        CHECK(v.tc == l.tc && v.start == l.start && v.pos == l.pos && v.verdict == l.words);
+        CHECK(v.words - v.verdict == (b + 7) / 8 && (v.words - v.verdict) * 8 >= b);
+        CHECK(v.words * 8 <= (UNITIG_NODE_BYTES + UNITIG_VERDICT_BYTES) * b + 32);
     }
     {  // every word of a small layout belongs to exactly one array
         const uint64_t b = 7;
@@ -54,6 +66,13 @@ int main() {
         for (int a = 0; a < 8; a++)
             for (uint64_t w = 0; w < len[a]; w++) owner[at[a] + w]++;
         for (int o : owner) CHECK(o == 1);
+        // ... and of the layout with verdict bytes: one more word for seven of them
+        const UnitigLayout v = unitig_layout(b, true);
+        std::vector<int> owner_v(v.words, 0);
+        for (int a = 0; a < 8; a++)
+            for (uint64_t w = 0; w < len[a]; w++) owner_v[at[a] + w]++;
+        for (uint64_t w = 0; w < (b + 7) / 8; w++) owner_v[v.verdict + w]++;
+        for (int o : owner_v) CHECK(o == 1);
     }
     // the FASTA header
     char buf[160];

@@ -707,6 +707,75 @@ int kc_unitig_graph_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, 
 int kc_unitig_graph(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
                     kc_unitig_edge** edges, kc_cdbg_stats* stats);   /* kc_free all three */
 
+/* Graph cleaning: the graph of src's range without its short tips and its short isolated unitigs,
+ * as a new counted table -- the step Bifrost (-i, -d), Minia, MEGAHIT and Velvet run on the raw
+ * graph of sequencing reads before anything else.  All terms are kc_graph_device's and
+ * kc_unitig_graph_device's: node, range [min_count, max_count], side, edge bits, link, unitig,
+ * circular, unitig end.
+ *   degree        of an end of a unitig U of the range's graph: the popcount of the edge nibble of
+ *                 the end's node at the end's side.  Edge bits only count neighbours that are nodes
+ *                 of the range.  An open unitig has two ends; for n = 1 they are the two sides of
+ *                 its one node.
+ *   isolated      U is open and both ends have degree 0.
+ *   tip           U is open and exactly one end has degree 0.  A circular unitig is neither.
+ *   palindromes   no special case: a palindromic node's side-L neighbours are its side-R neighbours
+ *                 complemented, so its two nibbles have equal popcounts.  It can be isolated and can
+ *                 never be a tip.
+ *   self edges    the rule reads the edge bits alone: an end whose only edge leads back into U -- a
+ *                 hairpin, a homopolymer's self loop -- counts as connected.
+ *   guard         with max_mean != 0, U is removable only when count_sum(U) <= (uint64_t)max_mean * n
+ *                 (count_sum: kc_unitig.count_sum, the sum of T(c) over U's n nodes).
+ *   removal       U is removed when it is a tip, tip_max_nodes != 0, n <= tip_max_nodes and the guard
+ *                 passes, or when it is isolated, iso_max_nodes != 0, n <= iso_max_nodes and the guard
+ *                 passes.  0 switches a rule off; the customary value of both is k - 1 (Bifrost's
+ *                 -i -d: tips and isolated unitigs shorter than k k-mers).
+ *   order         every verdict is taken on the original graph, so all removals are simultaneous and
+ *                 the result depends on no order.  One consequence is left as it is: at a junction
+ *                 all of whose branches are short tips, all of them go.  Removing tips makes new,
+ *                 longer unitigs and sometimes new tips: rounds compose by calling it again on dst.
+ *   kept nodes    every node of a unitig that is not removed.  Each kept node's raw count (the
+ *                 slot's count, not T(c)) is added into dst exactly as kc_table_op_device adds its
+ *                 results: a fresh dst holds exactly the cleaned graph, repeated calls accumulate,
+ *                 kc_stats.inserted grows by the counts added, a dst that is too small makes
+ *                 kc_finish(dst) return KC_ERR_TABLE_FULL, and a compact snapshot of dst is dropped.
+ *                 K-mers of src outside the range are not nodes and are not copied; with both rules
+ *                 off the call copies the range's nodes.
+ *   statistics    dst == NULL fills only the statistics: that call sizes a destination.  nodes ==
+ *                 out_keys + tip_nodes + isolated_nodes always.
+ *   kc_clean_device  follows the *_device rule for both contexts as kc_table_op_device does and has
+ *                 no host wait; its node ids are sized by src's table slots, as
+ *                 kc_unitig_graph_device's.  dev_stats (device memory) may be NULL.
+ *   kc_clean      counts the ids first (the k-mers with T(c) >= min_count), runs the ranking once and
+ *                 waits for the answer; stats (host memory) may be NULL.
+ * Errors: KC_ERR_ARG for dst == src, a different k or device, reserved != 0, min_count above a
+ * non-zero max_count, k < 2, a NULL src or desc; KC_ERR_STATE when either context has no table or a
+ * failed pass left it incomplete; KC_ERR_NOMEM when the scratch does not fit, reported before any
+ * kernel of the call (kc_clean: of the ranking) is launched.  The message goes on dst, or on src when
+ * dst is NULL.  An emptied src gives all-zero statistics and adds nothing.  src's table and kc_stats
+ * never change.
+ * Method: kc_unitigs_device's ranking and its records' kernel as they are, then one pass over the
+ * node ids in which the node at position 0 of every unitig reads its two end states, tells open from
+ * circular by their successors, reads the two ends' edge nibbles and writes the verdict at its id,
+ * and one pass in which every kept node reads its slot's key and count word and inserts them into
+ * dst.  The verdict costs one byte per id on top of kc_unitigs*'s scratch of src, which only these
+ * two calls allocate:
+ *   scratch = 5 * table_slots + 141 * ids bytes,  ids as for kc_unitigs* (< 2^30, else KC_ERR_NOMEM). */
+typedef struct {            /* 24 bytes */
+    uint32_t min_count, max_count;   /* the range, as kc_graph_device's */
+    uint32_t tip_max_nodes;          /* 0: tips are kept */
+    uint32_t iso_max_nodes;          /* 0: isolated unitigs are kept */
+    uint32_t max_mean;               /* 0: no guard */
+    uint32_t reserved;               /* 0 */
+} kc_clean_desc;
+typedef struct {            /* 64 bytes */
+    uint64_t unitigs, nodes;         /* of the range's graph: kc_unitig_stats' */
+    uint64_t tips, tip_nodes;        /* removed tips and their nodes */
+    uint64_t isolated, isolated_nodes;   /* removed isolated unitigs and their nodes */
+    uint64_t out_keys, out_sum;      /* kept nodes and the sum of their raw counts (added to dst when dst != NULL) */
+} kc_clean_stats;
+int kc_clean_device(kc_ctx* dst, kc_ctx* src, const kc_clean_desc* d, kc_clean_stats* dev_stats, void* hip_stream);
+int kc_clean(kc_ctx* dst, kc_ctx* src, const kc_clean_desc* d, kc_clean_stats* stats);
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
