@@ -44,25 +44,31 @@ UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound, bool with_verdict) {
     return u;
 }
 
+uint32_t* unitig_anchors(const kc_ctx* c, const UnitigBufs& u) {
+    uint64_t* b = c->d_unitig_node;
+    return reinterpret_cast<uint32_t*>(b + unitig_layout(u.bound, true, true).anchors);
+}
+
 // The ranking on s for up to `bound` nodes (the caller has joined s): the scratch first -- a failure
 // is reported before any kernel of the call is launched -- then the three sweeps and the jump
 // launches.  Leaves the views and the rounds for unitig_write.  with_rec: the record indices of
-// kc_unitig_graph*; with_verdict: the verdict bytes of kc_clean* (kc_api_clean.cpp).
+// kc_unitig_graph*; with_verdict: the verdict bytes of kc_clean* (kc_api_clean.cpp) and of
+// kc_pop_bubbles* (kc_api_bubble.cpp), whose anchors (with_anchors) lie behind them.
 int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u,
-                int* rounds, bool with_rec, bool with_verdict) {
+                int* rounds, bool with_rec, bool with_verdict, bool with_anchors) {
     const uint64_t slots = c->nbuckets * (uint64_t)c->S;
     bound = std::max<uint64_t>(1, std::min(bound, slots));
     if (bound >= UNITIG_MAX_BOUND)
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: " + std::to_string(bound) + " node ids do not fit 32-bit states (the "
                                      "device form sizes by the table's slots, kc_unitigs by the k-mers from min_count on)");
-    const uint64_t words = unitig_layout(bound, with_verdict).words;
+    const uint64_t words = unitig_layout(bound, with_verdict, with_anchors).words;
     if (c->d_graph_edges.capacity() < slots || c->d_unitig_ids.capacity() < slots || c->d_unitig_node.capacity() < words ||
         (with_rec && c->d_unitig_rec.capacity() < bound))
-        make_room(c, unitig_scratch_bytes(slots, bound, with_rec, with_verdict));
+        make_room(c, unitig_scratch_bytes(slots, bound, with_rec, with_verdict, with_anchors));
     if (!c->d_graph_edges.reserve(slots) || !c->d_unitig_ids.reserve(slots) || !c->d_unitig_node.reserve(words) ||
         !c->d_unitig_ctl.reserve(UNITIG_CTL_WORDS) || (with_rec && !c->d_unitig_rec.reserve(bound)))
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: scratch allocation failed (" +
-                                     std::to_string(unitig_scratch_bytes(slots, bound, with_rec, with_verdict)) + " bytes)");
+                                     std::to_string(unitig_scratch_bytes(slots, bound, with_rec, with_verdict, with_anchors)) + " bytes)");
     *u = unitig_bufs(c, bound, with_verdict);
     *rounds = unitig_rounds(bound);
     HIPCHK(c, hipMemsetAsync(u->ctl, 0, UNITIG_CTL_WORDS * sizeof(unsigned long long), s));

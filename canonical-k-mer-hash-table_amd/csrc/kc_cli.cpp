@@ -105,6 +105,13 @@ struct Args {
     bool clean_tips_set = false, clean_iso_set = false, clean_dep_set = false, clean_min_set = false;
     std::string clean_out, clean_stats;
     bool cleaning() const { return clean_tips_set || clean_iso_set; }
+    // --pop-bubbles N [--pop-max-diff D] [--pop-max-mean M] [--pop-rounds R] [--pop-min N] [--pop-max N]
+    // [--pop-out FILE] [--pop-stats FILE]: bubble popping (kc_pop_bubbles) of the counted table -- of
+    // the cleaned one when --clean-* are given too -- into a new one, R rounds at the most, which
+    // --graph, --unitigs and --gfa then read.  The range as for --clean-min / --clean-max.
+    unsigned long long pop_nodes = 0, pop_max_diff = 0, pop_max_mean = 0, pop_rounds = 1, pop_min = 0, pop_max = 0;
+    bool pop_set = false, pop_dep_set = false, pop_min_set = false;
+    std::string pop_out, pop_stats;
 };
 
 const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
@@ -173,7 +180,18 @@ void usage(const char* prog) {
                  "  --clean-min,--clean-max UINT\n"
                  "                              a k-mer is a node when its count is in this range (def. the -a value and up)\n"
                  "  --clean-out FILE            write every k-mer of the cleaned table, as -o writes the counted one's\n"
-                 "  --clean-stats FILE          a line of \"<name> <value>\" pairs per round\n\n"
+                 "  --clean-stats FILE          a line of \"<name> <value>\" pairs per round\n"
+                 "  --pop-bubbles UINT          pop the graph's bubbles (after the --clean-* rounds, on the table those\n"
+                 "                              left): of the unitigs of at most this many k-mers (k is customary) that\n"
+                 "                              run between the same two unitig ends, all but the one with the highest\n"
+                 "                              mean count go; --graph, --unitigs and --gfa then read the result\n"
+                 "  --pop-max-diff UINT         ... when their lengths differ by at most this many k-mers (def. 0)\n"
+                 "  --pop-max-mean UINT         never pop a unitig whose mean count is above this (def. no guard)\n"
+                 "  --pop-rounds UINT           popping rounds, each on the result of the one before; they stop early\n"
+                 "                              after a round that pops nothing (def. 1)\n"
+                 "  --pop-min,--pop-max UINT    a k-mer is a node when its count is in this range (def. the -a value and up)\n"
+                 "  --pop-out FILE              write every k-mer of the popped table, as -o writes the counted one's\n"
+                 "  --pop-stats FILE            a line of \"<name> <value>\" pairs per round\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -408,6 +426,22 @@ int parse(int argc, char** argv, Args* a) {
             } else if (o == "--clean-out" || o == "--clean-stats") {
                 (o == "--clean-out" ? a->clean_out : a->clean_stats) = v;
                 a->clean_dep_set = true;
+            } else if (o == "--pop-bubbles" || o == "--pop-max-diff" || o == "--pop-max-mean" || o == "--pop-rounds" ||
+                       o == "--pop-min" || o == "--pop-max") {
+                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
+                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
+                if (o == "--pop-bubbles") {
+                    a->pop_nodes = u;
+                    a->pop_set = true;
+                } else {
+                    (o == "--pop-max-diff" ? a->pop_max_diff : o == "--pop-max-mean" ? a->pop_max_mean
+                     : o == "--pop-rounds" ? a->pop_rounds : o == "--pop-min" ? a->pop_min : a->pop_max) = u;
+                    a->pop_dep_set = true;
+                    if (o == "--pop-min") a->pop_min_set = true;
+                }
+            } else if (o == "--pop-out" || o == "--pop-stats") {
+                (o == "--pop-out" ? a->pop_out : a->pop_stats) = v;
+                a->pop_dep_set = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -480,6 +514,13 @@ int parse(int argc, char** argv, Args* a) {
         return cli_error(kValidation, "--clean-min: a minimum above its maximum");
     if (a->clean_rounds < 1) return cli_error(kValidation, "--clean-rounds: Value 0 not in range 1 to inf");
     if (a->cleaning() && !a->op_name.empty()) return cli_error(kExcludes, "--clean-tips/--clean-isolated exclude --op");
+    if (a->pop_dep_set && !a->pop_set)
+        return cli_error(kRequires, "--pop-max-diff/--pop-max-mean/--pop-rounds/--pop-min/--pop-max/--pop-out/--pop-stats "
+                                    "require --pop-bubbles");
+    if (!a->pop_min_set) a->pop_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
+    if (a->pop_max && a->pop_min > a->pop_max) return cli_error(kValidation, "--pop-min: a minimum above its maximum");
+    if (a->pop_rounds < 1) return cli_error(kValidation, "--pop-rounds: Value 0 not in range 1 to inf");
+    if (a->pop_set && !a->op_name.empty()) return cli_error(kExcludes, "--pop-bubbles excludes --op");
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -1399,7 +1440,64 @@ int main(int argc, char** argv) {
         if (sf && std::fclose(sf) != 0) { std::cerr << "cannot write " << a.clean_stats << std::endl; gdie("graph cleaning"); }
         if (!a.clean_out.empty() && kc_write(gctx, a.clean_out.c_str()) != KC_OK) gdie("writing the cleaned k-mers");
     }
-    if (!a.graph.empty() || !a.graph_stats.empty()) {  // extension: the de Bruijn graph of the counted (or cleaned) k-mers
+    // --pop-bubbles (extension): up to --pop-rounds rounds of bubble popping on the table the cleaning
+    // left (or the counted one), each into a new table as above
+    if (a.pop_set) {
+        FILE* sf = nullptr;
+        if (!a.pop_stats.empty() && !(sf = std::fopen(a.pop_stats.c_str(), "w"))) {
+            std::cerr << "cannot write " << a.pop_stats << std::endl;
+            if (gctx != ctx) kc_destroy(gctx);
+            kc_destroy(ctx);
+            return 1;
+        }
+        kc_bubble_desc bd;
+        std::memset(&bd, 0, sizeof bd);
+        bd.min_count = (uint32_t)a.pop_min;
+        bd.max_count = (uint32_t)a.pop_max;
+        bd.max_nodes = (uint32_t)a.pop_nodes;
+        bd.max_diff = (uint32_t)a.pop_max_diff;
+        bd.max_mean = (uint32_t)a.pop_max_mean;
+        for (unsigned long long round = 1; round <= a.pop_rounds; round++) {
+            kc_bubble_stats bs;
+            if (kc_pop_bubbles(nullptr, gctx, &bd, &bs) != KC_OK) gdie("bubble popping");
+            kc_config rcfg = cfg;
+            rcfg.bf_enable = 0;
+            rcfg.est_unique = 0;
+            rcfg.min_abundance = 1;
+            rcfg.table_slots = bs.out_keys + bs.out_keys / 8 + 4096;
+            rcfg.batch_bytes = 1 << 20;  // (nothing is staged into it)
+            kc_ctx* next = nullptr;
+            if (kc_create(&rcfg, &next) != KC_OK) {
+                std::cerr << "kc_create (bubble popping): " << kc_last_error(nullptr) << std::endl;
+                if (gctx != ctx) kc_destroy(gctx);
+                kc_destroy(ctx);
+                return 1;
+            }
+            kc_stats str;
+            if (kc_pop_bubbles(next, gctx, &bd, &bs) != KC_OK || kc_finish(next, &str) != KC_OK) {
+                std::cerr << "bubble popping: " << kc_last_error(next) << std::endl;
+                kc_destroy(next);
+                if (gctx != ctx) kc_destroy(gctx);
+                kc_destroy(ctx);
+                return 1;
+            }
+            if (gctx != ctx) kc_destroy(gctx);
+            gctx = next;
+            if (sf)
+                std::fprintf(sf, "round %llu unitigs %llu nodes %llu branches %llu parallel %llu popped %llu popped_nodes %llu "
+                                 "out_keys %llu out_sum %llu\n", round, (unsigned long long)bs.unitigs,
+                             (unsigned long long)bs.nodes, (unsigned long long)bs.branches, (unsigned long long)bs.parallel,
+                             (unsigned long long)bs.popped, (unsigned long long)bs.popped_nodes,
+                             (unsigned long long)bs.out_keys, (unsigned long long)bs.out_sum);
+            std::cout << "Bubble popping round " << round << ": " << bs.unitigs << " unitigs, " << bs.nodes << " nodes, "
+                      << bs.branches << " branches, " << bs.parallel << " of them parallel; popped " << bs.popped << " ("
+                      << bs.popped_nodes << " nodes); kept " << bs.out_keys << " k-mers in " << str.table_slots << " slots\n";
+            if (!bs.popped) break;
+        }
+        if (sf && std::fclose(sf) != 0) { std::cerr << "cannot write " << a.pop_stats << std::endl; gdie("bubble popping"); }
+        if (!a.pop_out.empty() && kc_write(gctx, a.pop_out.c_str()) != KC_OK) gdie("writing the popped k-mers");
+    }
+    if (!a.graph.empty() || !a.graph_stats.empty()) {  // extension: the de Bruijn graph of the counted (or cleaned, popped) k-mers
         uint64_t* grec = nullptr;
         uint64_t gn = 0;
         kc_graph_stats gst;
@@ -1517,7 +1615,7 @@ int main(int argc, char** argv) {
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
     if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty() || !a.graph.empty() ||
-        !a.graph_stats.empty() || !a.unitigs.empty() || !a.gfa.empty() || a.cleaning())
+        !a.graph_stats.empty() || !a.unitigs.empty() || !a.gfa.empty() || a.cleaning() || a.pop_set)
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
                   << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")

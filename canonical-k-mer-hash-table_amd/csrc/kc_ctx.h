@@ -451,12 +451,15 @@ bool use_partitioned_bloom(const kc_ctx* c, uint64_t syms);
 int sync_for_read(kc_ctx* c);
 void make_room(kc_ctx* c, uint64_t bytes);
 void drop_compact(kc_ctx* c);
-// kc_api_unitig.cpp (shared with kc_api_clean.cpp: the checks, the ids' bound of a host form, the ranking)
+// kc_api_unitig.cpp (shared with kc_api_clean.cpp and kc_api_bubble.cpp: the checks, the ids' bound of
+// a host form, the ranking)
 UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound, bool with_verdict = false);
 int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count);
 int unitig_bound(kc_ctx* c, uint32_t min_count, unsigned long long* bound);
 int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u, int* rounds,
-                bool with_rec = false, bool with_verdict = false);
+                bool with_rec = false, bool with_verdict = false, bool with_anchors = false);
+// the anchors of kc_pop_bubbles* in the scratch a ranking with_verdict and with_anchors left (u.bound ids)
+uint32_t* unitig_anchors(const kc_ctx* c, const UnitigBufs& u);
 // kc_api_pass.cpp
 int flush_host(kc_ctx* c);
 int device_pass(kc_ctx* c, const uint8_t* img, const kc_chunk* chunks, size_t n, int fmt, int pass, hipStream_t s);

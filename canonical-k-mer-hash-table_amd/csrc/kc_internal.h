@@ -545,6 +545,12 @@ __device__ inline uint64_t unitig_nodes(const UnitigBufs& u) {
     const unsigned long long n = u.ctl[UC_NODES];
     return n < u.bound ? n : u.bound;
 }
+// the degree of the unitig end at state x (< 2 * nodes): the edge nibble of its node at its exit side
+__device__ __forceinline__ uint32_t unitig_end_degree(const UnitigBufs& u, uint32_t x, uint64_t n_slots) {
+    const uint64_t slot = u.slot_of[x >> 1];
+    if (slot >= n_slots) return 1;  // (cannot be: it then counts as connected, and nothing is removed for it)
+    return (uint32_t)__popc(((uint32_t)u.edges[slot] >> (4 * (x & 1))) & 15);
+}
 template <int W>
 struct UnitigOps {
     // edges, dense ids, successors and the first states (three sweeps of the table)
@@ -590,9 +596,26 @@ struct CleanOps {
 hipError_t launch_clean(TableView src, TableView dst, UnitigBufs u, DevCounters* ctr, unsigned long long* stats,
                         hipStream_t s);
 
+// Bubble popping (include/kc_api.h kc_pop_bubbles_device; kc_bubble_impl.h), after a ranking with
+// verdict bytes and launch_unitig_heads of the same UnitigBufs, and before launch_clean, which drops
+// the nodes of every unitig whose verdict is not CLEAN_KEEP.  anc: 2 * u.bound words, [2 start id +
+// e] the anchor of end e of the branch that starts there (2 * the neighbour's node id + its facing
+// side), UNITIG_NO_ID at every other id.  pop zeroes the verdict bytes, fills anc and writes
+// CLEAN_BUBBLE at the start id of every popped branch; stats (nullptr: none) receives the first six
+// words of kc_bubble_stats, added to.
+constexpr uint8_t CLEAN_BUBBLE = 3;
+struct BubbleRule {
+    uint32_t max_nodes, max_diff, max_mean;  // kc_bubble_desc's
+};
+template <int W>
+struct BubbleOps {
+    static hipError_t pop(TableView src, int k, UnitigBufs u, int rounds, uint32_t* anc, BubbleRule rule,
+                          unsigned long long* stats, hipStream_t s);
+};
+
 // Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip, kc_unitig.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
-// JoinOps, GraphOps, UnitigOps, CleanOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_clean_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// JoinOps, GraphOps, UnitigOps, CleanOps, BubbleOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_clean_w.hip, kc_bubble_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

@@ -241,13 +241,6 @@ __global__ __launch_bounds__(UT) void k_unitig_heads(UnitigBufs u, int k, int j,
     }
 }
 
-// the degree of the unitig end at state x (< 2 * nodes): the edge nibble of its node at its exit side
-DEV uint32_t unitig_end_degree(const UnitigBufs& u, uint32_t x, uint64_t n_slots) {
-    const uint64_t slot = u.slot_of[x >> 1];
-    if (slot >= n_slots) return 1;  // (cannot be: it then counts as connected, and nothing is removed for it)
-    return (uint32_t)__popc(((uint32_t)u.edges[slot] >> (4 * (x & 1))) & 15);
-}
-
 __global__ __launch_bounds__(UT) void k_unitig_verdict(UnitigBufs u, int j, uint64_t n_slots, CleanRule rule,
                                                        unsigned long long* __restrict__ stats) {
     const uint64_t n_nodes = unitig_nodes(u), n_states = 2 * n_nodes;

@@ -18,6 +18,8 @@ constexpr uint64_t UNITIG_SLOT_BYTES = 5, UNITIG_NODE_BYTES = 140;
 constexpr uint64_t UNITIG_REC_BYTES = 4;
 // kc_clean* only: the verdict of the unitig that starts at the node id
 constexpr uint64_t UNITIG_VERDICT_BYTES = 1;
+// kc_pop_bubbles* only: the two anchors of the unitig that starts at the node id
+constexpr uint64_t UNITIG_ANCHOR_BYTES = 8;
 
 // jump launches of one ranking over up to `bound` nodes: ceil(log2(2 * bound)) + 1, round r covers
 // paths of 2^(r + 1) states
@@ -28,11 +30,12 @@ inline int unitig_rounds(uint64_t bound) {
     return lg + 1;
 }
 
-// the scratch of a call (with_rec: of kc_unitig_graph*, with_verdict: of kc_clean*), control words
-// aside; 0: it overflows 64 bits
+// the scratch of a call (with_rec: of kc_unitig_graph*, with_verdict: of kc_clean* and
+// kc_pop_bubbles*, with_anchors: of kc_pop_bubbles*), control words aside; 0: it overflows 64 bits
 inline uint64_t unitig_scratch_bytes(uint64_t table_slots, uint64_t bound, bool with_rec = false,
-                                     bool with_verdict = false) {
-    const uint64_t node = UNITIG_NODE_BYTES + (with_rec ? UNITIG_REC_BYTES : 0) + (with_verdict ? UNITIG_VERDICT_BYTES : 0);
+                                     bool with_verdict = false, bool with_anchors = false) {
+    const uint64_t node = UNITIG_NODE_BYTES + (with_rec ? UNITIG_REC_BYTES : 0) + (with_verdict ? UNITIG_VERDICT_BYTES : 0) +
+                          (with_anchors ? UNITIG_ANCHOR_BYTES : 0);
     if (table_slots > ~0ULL / UNITIG_SLOT_BYTES || bound > ~0ULL / node) return 0;
     const uint64_t a = table_slots * UNITIG_SLOT_BYTES, b = bound * node;
     return a + b < a ? 0 : a + b;
@@ -41,12 +44,13 @@ inline uint64_t unitig_scratch_bytes(uint64_t table_slots, uint64_t bound, bool 
 // The per-node arrays in one block of 64-bit words, the widest first so that each is aligned:
 // offsets in words of the two state buffers (6 words a node each), slot_of, off (2), succ (1), then
 // the three 32-bit arrays tc, start and pos (half a word a node, rounded up) and, with_verdict
-// (kc_clean* only), the verdict bytes (an eighth of a word a node, rounded up) behind them: the
-// other calls' offsets and words are the same with or without
+// (kc_clean* and kc_pop_bubbles*), the verdict bytes (an eighth of a word a node, rounded up) behind
+// them, and, with_anchors (kc_pop_bubbles* only), two 32-bit anchors a node (one word) behind those:
+// the other calls' offsets and words are the same with or without
 struct UnitigLayout {
-    uint64_t st0, st1, slot_of, off, succ, tc, start, pos, verdict, words;
+    uint64_t st0, st1, slot_of, off, succ, tc, start, pos, verdict, anchors, words;
 };
-inline UnitigLayout unitig_layout(uint64_t bound, bool with_verdict = false) {
+inline UnitigLayout unitig_layout(uint64_t bound, bool with_verdict = false, bool with_anchors = false) {
     const uint64_t half = (bound + 1) / 2;
     UnitigLayout l;
     l.st0 = 0;
@@ -58,7 +62,8 @@ inline UnitigLayout unitig_layout(uint64_t bound, bool with_verdict = false) {
     l.start = l.tc + half;
     l.pos = l.start + half;
     l.verdict = l.pos + half;
-    l.words = l.verdict + (with_verdict ? (bound + 7) / 8 : 0);
+    l.anchors = l.verdict + (with_verdict ? (bound + 7) / 8 : 0);
+    l.words = l.anchors + (with_anchors ? bound : 0);
     return l;
 }
 

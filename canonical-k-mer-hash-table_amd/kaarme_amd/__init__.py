@@ -68,6 +68,7 @@ EXPORTS = (
     "kc_unitigs_device", "kc_unitigs",
     "kc_unitig_graph_device", "kc_unitig_graph",
     "kc_clean_device", "kc_clean",
+    "kc_pop_bubbles_device", "kc_pop_bubbles",
 )
 # kc_graph* node flags (KC_GRAPH_*): bits 0-7 the edges -- bit y: canon(c[1:] + y) is a node (side
 # R), bit 4 + y: canon(y + c[:-1]) is a node (side L) -- then the two unitig links and the node bit
@@ -215,6 +216,21 @@ class kc_clean_stats(ctypes.Structure):  # 64 bytes
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class kc_bubble_desc(ctypes.Structure):  # 24 bytes
+    _fields_ = [(n, ctypes.c_uint32) for n in ("min_count", "max_count", "max_nodes", "max_diff", "max_mean", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_bubble_stats(ctypes.Structure):  # 64 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("unitigs", "nodes", "branches", "parallel", "popped", "popped_nodes",
+                                               "out_keys", "out_sum")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class kc_correct_stat(ctypes.Structure):  # 16 bytes
     _fields_ = [(n, ctypes.c_uint32) for n in ("candidates", "corrected", "ambiguous", "dropped")]
 
@@ -334,6 +350,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                              ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(kc_unitig_stats)]),
         "kc_clean_device": (I32, [P, P, ctypes.POINTER(kc_clean_desc), P, P]),
         "kc_clean": (I32, [P, P, ctypes.POINTER(kc_clean_desc), ctypes.POINTER(kc_clean_stats)]),
+        "kc_pop_bubbles_device": (I32, [P, P, ctypes.POINTER(kc_bubble_desc), P, P]),
+        "kc_pop_bubbles": (I32, [P, P, ctypes.POINTER(kc_bubble_desc), ctypes.POINTER(kc_bubble_stats)]),
         "kc_unitig_graph_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, U64, P, P]),
         "kc_unitig_graph": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
                                   ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
@@ -1026,6 +1044,30 @@ class KmerCounter:
         self._chk(self.lib.kc_clean(self._ctx, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_clean")
         return st.as_dict()
 
+    # -- bubble popping (kc_pop_bubbles*): this counter is the destination
+    def pop_bubbles_device(self, src: "KmerCounter", min_count: int = 1, max_count: int = 0, max_nodes: int = 0,
+                           max_diff: int = 0, max_mean: int = 0, stats_ptr: int = 0, stream: int = 0):
+        """self += the graph of src's k-mers with min_count <= T(c) <= max_count without the weaker of
+        its parallel unitigs: a branch (both ends of degree 1) of at most max_nodes nodes (0: nothing
+        is popped; k is customary) is dropped when a branch between the same two unitig ends, of at
+        most max_nodes nodes and at most max_diff nodes longer or shorter, has the higher mean T(c)
+        (or the same and the smaller name); none is dropped whose mean T(c) is above max_mean (0: no
+        guard); raw counts, all in HBM.  stats_ptr: 64 bytes of device memory for the
+        kc_bubble_stats (0: none); enqueued on `stream`, no wait."""
+        d = _bubble_desc(min_count, max_count, max_nodes, max_diff, max_mean)
+        self._chk(self.lib.kc_pop_bubbles_device(self._ctx, src._ctx, ctypes.byref(d), ctypes.c_void_p(stats_ptr or None),
+                                                 ctypes.c_void_p(stream or None)), "kc_pop_bubbles_device")
+
+    def pop_bubbles(self, src: "KmerCounter", min_count: int = 1, max_count: int = 0, max_nodes: int = 0,
+                    max_diff: int = 0, max_mean: int = 0) -> dict:
+        """pop_bubbles_device that waits; returns the statistics: unitigs and nodes of the range's
+        graph, branches, parallel (branches with a parallel branch, whatever the limits), popped and
+        popped_nodes (what was dropped), out_keys and out_sum (the kept nodes and their raw counts,
+        added here)."""
+        d, st = _bubble_desc(min_count, max_count, max_nodes, max_diff, max_mean), kc_bubble_stats()
+        self._chk(self.lib.kc_pop_bubbles(self._ctx, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_pop_bubbles")
+        return st.as_dict()
+
     def compact_read(self, info: dict):
         """(slot words, secondary-array words) as uint64 arrays."""
         W = self.lib.kc_key_words(self._ctx)
@@ -1109,6 +1151,51 @@ def clean_rounds(src: KmerCounter, rounds: int, **rule) -> Tuple[KmerCounter, Li
         cur = dst
         stats.append(st)
         if st["tips"] == 0 and st["isolated"] == 0:
+            break
+    return cur, stats
+
+
+def _bubble_desc(min_count, max_count, max_nodes, max_diff, max_mean) -> kc_bubble_desc:
+    return kc_bubble_desc(int(min_count), int(max_count), int(max_nodes), int(max_diff), int(max_mean), 0)
+
+
+def bubble_stats(src: KmerCounter, min_count: int = 1, max_count: int = 0, max_nodes: int = 0, max_diff: int = 0,
+                 max_mean: int = 0) -> dict:
+    """The statistics of KmerCounter.pop_bubbles without a destination (kc_pop_bubbles with dst NULL):
+    nothing is inserted anywhere, and out_keys sizes a destination."""
+    d, st = _bubble_desc(min_count, max_count, max_nodes, max_diff, max_mean), kc_bubble_stats()
+    src._chk(src.lib.kc_pop_bubbles(None, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_pop_bubbles")
+    return st.as_dict()
+
+
+def pop_rounds(src: KmerCounter, rounds: int, **rule) -> Tuple[KmerCounter, List[dict]]:
+    """Up to `rounds` rounds of bubble popping, each on the result of the one before (popping joins
+    unitigs, and a longer unitig can be an arm of a wider bubble): (the last round's table, the
+    statistics of every round run).  rule: pop_bubbles()'s keywords, the same in every round.  A
+    round first asks for the statistics alone, creates a table of out_keys + out_keys / 8 + 4096
+    slots (src's k, mode, min_abundance and device; no Bloom filter, a 1 MiB stage: it is read, not
+    counted into) and pops into it; the intermediate table before it is closed (src never is).
+    The rounds stop early after one that pops nothing.  The caller closes the result."""
+    if rounds < 1:
+        raise ValueError("pop_rounds: rounds must be at least 1")
+    cur, stats = src, []
+    for _ in range(rounds):
+        n = bubble_stats(cur, **rule)["out_keys"]
+        dst = KmerCounter(dataclasses.replace(src.cfg, table_slots=n + n // 8 + 4096, bf_enable=False, est_unique=0,
+                                              batch_bytes=1 << 20))
+        try:
+            st = dst.pop_bubbles(cur, **rule)
+            dst.finish()
+        except Exception:
+            dst.close()
+            if cur is not src:
+                cur.close()
+            raise
+        if cur is not src:
+            cur.close()
+        cur = dst
+        stats.append(st)
+        if st["popped"] == 0:
             break
     return cur, stats
 

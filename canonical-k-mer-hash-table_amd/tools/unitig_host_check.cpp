@@ -42,6 +42,11 @@ int main() {
     CHECK(unitig_scratch_bytes(268435456ULL, 268435456ULL, false, true) == 146 * 268435456ULL);
     CHECK(unitig_scratch_bytes(1, ~0ULL / 141 + 1, false, true) == 0 && unitig_scratch_bytes(1, ~0ULL / 141 + 1) != 0);
     CHECK(unitig_scratch_bytes(1 << 20, 1000, true, true) == 5ULL * (1 << 20) + 145 * 1000);
+    // ... of kc_pop_bubbles*: the verdict byte and the two anchors per id on top
+    CHECK(unitig_scratch_bytes(1 << 20, 1000, false, true, true) == 5ULL * (1 << 20) + 149 * 1000);
+    CHECK(unitig_scratch_bytes(268435456ULL, 268435456ULL, false, true, true) == 154 * 268435456ULL);
+    CHECK(unitig_scratch_bytes(1, ~0ULL / 149 + 1, false, true, true) == 0 && unitig_scratch_bytes(1, ~0ULL / 149 + 1) != 0);
+    CHECK(unitig_scratch_bytes(1 << 20, 1000, false, false, true) == 5ULL * (1 << 20) + 148 * 1000);
     // the layout: disjoint arrays, in order, inside `words`, and within the bytes the header states
     for (uint64_t b : std::vector<uint64_t>{1, 2, 3, 1000, 86000001, UNITIG_MAX_BOUND - 1}) {
         const UnitigLayout l = unitig_layout(b);
@@ -56,6 +61,13 @@ int main() {
         CHECK(v.tc == l.tc && v.start == l.start && v.pos == l.pos && v.verdict == l.words);
         CHECK(v.words - v.verdict == (b + 7) / 8 && (v.words - v.verdict) * 8 >= b);
         CHECK(v.words * 8 <= (UNITIG_NODE_BYTES + UNITIG_VERDICT_BYTES) * b + 32);
+        CHECK(l.anchors == l.words && v.anchors == v.words);  // (no anchors unless asked for)
+        // with the anchors too: the verdict layout as it was, one word a node behind the verdict bytes
+        const UnitigLayout a = unitig_layout(b, true, true);
+        CHECK(a.st0 == v.st0 && a.st1 == v.st1 && a.slot_of == v.slot_of && a.off == v.off && a.succ == v.succ);
+        CHECK(a.tc == v.tc && a.start == v.start && a.pos == v.pos && a.verdict == v.verdict && a.anchors == v.words);
+        CHECK(a.words - a.anchors == b && (a.words - a.anchors) * 8 == UNITIG_ANCHOR_BYTES * b);
+        CHECK(a.words * 8 <= (UNITIG_NODE_BYTES + UNITIG_VERDICT_BYTES + UNITIG_ANCHOR_BYTES) * b + 32);
     }
     {  // every word of a small layout belongs to exactly one array
         const uint64_t b = 7;
@@ -73,6 +85,14 @@ int main() {
             for (uint64_t w = 0; w < len[a]; w++) owner_v[at[a] + w]++;
         for (uint64_t w = 0; w < (b + 7) / 8; w++) owner_v[v.verdict + w]++;
         for (int o : owner_v) CHECK(o == 1);
+        // ... and with the anchors: b more words
+        const UnitigLayout a = unitig_layout(b, true, true);
+        std::vector<int> owner_a(a.words, 0);
+        for (int x = 0; x < 8; x++)
+            for (uint64_t w = 0; w < len[x]; w++) owner_a[at[x] + w]++;
+        for (uint64_t w = 0; w < (b + 7) / 8; w++) owner_a[a.verdict + w]++;
+        for (uint64_t w = 0; w < b; w++) owner_a[a.anchors + w]++;
+        for (int o : owner_a) CHECK(o == 1);
     }
     // the FASTA header
     char buf[160];

@@ -776,6 +776,83 @@ typedef struct {            /* 64 bytes */
 int kc_clean_device(kc_ctx* dst, kc_ctx* src, const kc_clean_desc* d, kc_clean_stats* dev_stats, void* hip_stream);
 int kc_clean(kc_ctx* dst, kc_ctx* src, const kc_clean_desc* d, kc_clean_stats* stats);
 
+/* Bubble popping: the graph of src's range without the weaker of its parallel unitigs, as a new
+ * counted table -- the step that goes with tip clipping in Velvet (tour bus), Minia, MEGAHIT (merge
+ * bubbles) and SPAdes (bulge remover).  A substitution in the middle of a read leaves a path of k
+ * error k-mers beside the true path between the same two junctions, an indel one of about k - 1, a
+ * heterozygous site two real paths.  All terms are kc_graph_device's, kc_unitig_graph_device's and
+ * kc_clean_device's: node, range [min_count, max_count], side, edge bits, unitig, unitig end, degree
+ * of an end, palindromic unitig, circular, edge (from, from_rev, to, to_rev).
+ *   branch        U is a branch when it is open and not palindromic, both its ends have degree
+ *                 exactly 1, and neither of its two edges leads to U itself.
+ *   anchor        the unitig end that an end of a branch is attached to: for the edge (U, from_rev, V,
+ *                 to_rev) the anchor is (V, 1 - to_rev), the from_rev value of the mirror edge.  A
+ *                 palindromic V has one orientation, so its anchors all read (V, 1).  A branch has
+ *                 two anchors; if they are the same unitig end, U is not a branch.  An anchor end
+ *                 always has degree >= 2 (otherwise the link rule would have merged it), so an
+ *                 anchor is never itself a branch through that end.
+ *   parallel      two different branches with the same unordered pair of anchors.  At most four
+ *                 branches share an anchor end.
+ *   beats         U' beats U when count_sum(U') * n(U) > count_sum(U) * n(U'), compared exactly (the
+ *                 products need more than 64 bits), or the two products are equal and name(U') <
+ *                 name(U).  name(U) is the smaller of the canonical k-mer strings of U's two end
+ *                 nodes, in A < C < G < T order, as kc_dump writes keys; distinct unitigs have
+ *                 distinct names.
+ *   popped        U is popped when max_nodes != 0 and n(U) <= max_nodes, the guard passes (max_mean
+ *                 == 0 or count_sum(U) <= (uint64_t)max_mean * n(U)), and some branch U' exists that
+ *                 is parallel to U, has n(U') <= max_nodes, has |n(U) - n(U')| <= max_diff, and
+ *                 beats U.  max_diff = 0 means arms of equal length only (SNP bubbles); the
+ *                 customary max_nodes is k.
+ *   order         every verdict is taken on the one graph, so removals are simultaneous and depend
+ *                 on no order.  In every set of mutually parallel branches, the one that no other
+ *                 beats stays.  No anchor is removed.  Paths of more than one unitig (nested
+ *                 bubbles) are not looked at; popping joins unitigs, so rounds compose by calling it
+ *                 again on dst, and with kc_clean by calling one on the other's dst.
+ *   kept nodes    every node of a unitig that is not popped.  Each kept node's raw count (the
+ *                 slot's count, not T(c)) is added into dst exactly as kc_table_op_device adds its
+ *                 results: a fresh dst holds exactly the popped graph, repeated calls accumulate,
+ *                 kc_stats.inserted grows by the counts added, a dst that is too small makes
+ *                 kc_finish(dst) return KC_ERR_TABLE_FULL, and a compact snapshot of dst is dropped.
+ *                 K-mers of src outside the range are not nodes and are not copied; with max_nodes
+ *                 == 0 the call copies the range's nodes.
+ *   statistics    dst == NULL fills only the statistics: that call sizes a destination.  nodes ==
+ *                 out_keys + popped_nodes always.
+ *   kc_pop_bubbles_device  follows the *_device rule for both contexts as kc_table_op_device does and
+ *                 has no host wait; its node ids are sized by src's table slots, as
+ *                 kc_unitig_graph_device's.  dev_stats (device memory) may be NULL.
+ *   kc_pop_bubbles  counts the ids first (the k-mers with T(c) >= min_count), runs the ranking once
+ *                 and waits for the answer; stats (host memory) may be NULL.
+ * Errors: KC_ERR_ARG for dst == src, a different k or device, reserved != 0, min_count above a
+ * non-zero max_count, k < 2, a NULL src or desc; KC_ERR_STATE when either context has no table or a
+ * failed pass left it incomplete; KC_ERR_NOMEM when the scratch does not fit, reported before any
+ * kernel of the call (kc_pop_bubbles: of the ranking) is launched.  The message goes on dst, or on
+ * src when dst is NULL.  An emptied src gives all-zero statistics and adds nothing.  src's table and
+ * kc_stats never change.
+ * Method: kc_unitigs_device's ranking and its records' kernel as they are, then one pass over the
+ * node ids in which the node at position 0 of every unitig with two ends of degree 1 probes the one
+ * neighbour of each end and leaves the two anchors -- 2 * the neighbour's node id + its facing side
+ * -- at its id; one pass in which every branch walks the at most four edges of one of its anchor
+ * ends, probes each neighbour, compares that unitig's anchors with its own and writes the verdict;
+ * and kc_clean_device's copy of the kept nodes.  A branch costs at most six probes.  The anchors
+ * cost 8 bytes per id on top of kc_clean*'s scratch of src, which only these two calls allocate:
+ *   scratch = 5 * table_slots + 149 * ids bytes,  ids as for kc_unitigs* (< 2^30, else KC_ERR_NOMEM). */
+typedef struct {            /* 24 bytes */
+    uint32_t min_count, max_count;   /* the range, as kc_graph_device's */
+    uint32_t max_nodes;     /* 0: nothing is popped, the call copies the range's nodes */
+    uint32_t max_diff;      /* the most two arms' node counts may differ by; 0: equal lengths only */
+    uint32_t max_mean;      /* 0: no guard */
+    uint32_t reserved;      /* 0 */
+} kc_bubble_desc;
+typedef struct {            /* 64 bytes */
+    uint64_t unitigs, nodes;        /* of the range's graph: kc_unitig_stats' */
+    uint64_t branches;              /* unitigs that are branches */
+    uint64_t parallel;              /* branches with at least one parallel branch, whatever the limits */
+    uint64_t popped, popped_nodes;  /* popped branches and their nodes */
+    uint64_t out_keys, out_sum;     /* kept nodes and the sum of their raw counts (added to dst when dst != NULL) */
+} kc_bubble_stats;
+int kc_pop_bubbles_device(kc_ctx* dst, kc_ctx* src, const kc_bubble_desc* d, kc_bubble_stats* dev_stats, void* hip_stream);
+int kc_pop_bubbles(kc_ctx* dst, kc_ctx* src, const kc_bubble_desc* d, kc_bubble_stats* stats);
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
