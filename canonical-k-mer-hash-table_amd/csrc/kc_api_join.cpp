@@ -7,12 +7,6 @@
 
 static_assert(sizeof(kc_op_desc) == 24 && sizeof(kc_op_stats) == 40, "include/kc_api.h states these sizes");
 
-// the error of a call on `from` is reported on the context the caller reads (dst, else a)
-static int op_rc(kc_ctx* err, kc_ctx* from, int rc) {
-    if (rc && from != err) err->err = from->err;
-    return rc;
-}
-
 static bool op_is_union(int op) { return op == KC_OP_UNION_SUM || op == KC_OP_UNION_MAX; }
 
 // what both forms check before they touch the device; err receives the message
@@ -44,14 +38,14 @@ int kc_table_op_device(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, 
     if (rc) return rc;
     hipStream_t s = (hipStream_t)sp;
     for (kc_ctx* x : {dst, a, b != a ? b : nullptr})
-        if (x && (rc = op_rc(err, x, flush_host(x)))) return rc;
+        if (x && (rc = route_rc(err, x, flush_host(x)))) return rc;
     // one scope per distinct context: s waits for each one's stream, each then waits for s
     StreamScope on_a(a, s), on_b(b, s);  // (a == b: on_b is never joined)
-    if ((rc = op_rc(err, a, on_a.join()))) return rc;
-    if (b != a && (rc = op_rc(err, b, on_b.join()))) return rc;
+    if ((rc = route_rc(err, a, on_a.join()))) return rc;
+    if (b != a && (rc = route_rc(err, b, on_b.join()))) return rc;
     // an emptied operand holds nothing (and its memory is not read before it is zeroed)
-    if ((rc = op_rc(err, a, materialize_zero(a, s)))) return rc;
-    if ((rc = op_rc(err, b, materialize_zero(b, s)))) return rc;
+    if ((rc = route_rc(err, a, materialize_zero(a, s)))) return rc;
+    if ((rc = route_rc(err, b, materialize_zero(b, s)))) return rc;
     unsigned long long* st = reinterpret_cast<unsigned long long*>(dev_stats);
     if (st) HIPCHK(err, hipMemsetAsync(st, 0, sizeof(kc_op_stats), s));
     const uint32_t a_min = op->a_min ? op->a_min : 1, b_min = op->b_min ? op->b_min : 1;
@@ -64,18 +58,10 @@ int kc_table_op_device(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, 
             HIPCHK(err, launch_join(tb, ta, td, mb, ma, b_min, op->b_max, a_min, op->a_max, op->op, 1, ctr, st, s));
         return KC_OK;
     };
-    if (dst) {
-        // dst's host-side state as after kc_insert_counts_device's direct insert; the compact
-        // representation is a snapshot of the table before this call
-        if (dst->d_cwords) drop_compact(dst);
-        StreamScope on_d(dst, s);
-        rc = insert_on(dst, on_d, false, true, [&] { return materialize_zero(dst, s); }, work);
-    } else {
-        rc = work();
-    }
+    rc = write_dst(dst, s, work);
     if (rc) return rc;
-    if ((rc = op_rc(err, a, on_a.finish()))) return rc;
-    return op_rc(err, b, on_b.finish());
+    if ((rc = route_rc(err, a, on_a.finish()))) return rc;
+    return route_rc(err, b, on_b.finish());
 }
 
 int kc_table_op(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, kc_op_stats* stats) {
@@ -83,16 +69,8 @@ int kc_table_op(kc_ctx* dst, kc_ctx* a, kc_ctx* b, const kc_op_desc* op, kc_op_s
     if (!a || !b || !op) return err ? err->fail(KC_ERR_ARG, "kc_table_op: null operand or descriptor") : KC_ERR_ARG;
     int rc = op_check(err, dst, a, b, op);
     if (rc) return rc;
-    DevBuf<kc_op_stats> d;
-    if (stats && !d.reserve(1)) return err->fail(KC_ERR_NOMEM, "kc_table_op: statistics allocation failed");
-    hipStream_t s = err->stream;
-    rc = kc_table_op_device(dst, a, b, op, d, s);
-    hipError_t e = hipSuccess;
-    if (rc == KC_OK && stats) e = hipMemcpyAsync(stats, d, sizeof(kc_op_stats), hipMemcpyDeviceToHost, s);
-    const hipError_t e2 = hipStreamSynchronize(s);  // (also on an error: the kernels may still write d)
-    if (rc == KC_OK && (e != hipSuccess || e2 != hipSuccess))
-        rc = err->hipfail(e != hipSuccess ? e : e2, "kc_table_op: statistics copy");
-    return rc;
+    return stats_host_form(err, "kc_table_op", stats,
+                           [&](kc_op_stats* d, hipStream_t s) { return kc_table_op_device(dst, a, b, op, d, s); });
 }
 
 }  // extern "C"

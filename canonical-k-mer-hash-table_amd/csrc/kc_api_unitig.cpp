@@ -24,8 +24,12 @@ int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count) {
     return KC_OK;
 }
 
-UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound, bool with_verdict) {
-    const UnitigLayout l = unitig_layout(bound, with_verdict);
+static_assert(offsetof(kc_cdbg_stats, bases) == offsetof(kc_unitig_stats, bases) && offsetof(kc_cdbg_stats, max_nodes) == 4 * 8,
+              "kc_unitig_stats is the first five words of kc_cdbg_stats");
+
+// the views of c's scratch for `bound` node ids
+static UnitigRanked unitig_bufs(const kc_ctx* c, uint64_t bound, UnitigWants w) {
+    const UnitigLayout l = unitig_layout(bound, w);
     uint64_t* b = c->d_unitig_node;
     UnitigBufs u{};
     u.edges = c->d_graph_edges;
@@ -40,52 +44,43 @@ UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound, bool with_verdict) {
     u.start = reinterpret_cast<uint32_t*>(b + l.start);
     u.pos = reinterpret_cast<uint32_t*>(b + l.pos);
     u.ctl = c->d_unitig_ctl;
-    u.verdict = with_verdict ? reinterpret_cast<uint8_t*>(b + l.verdict) : nullptr;
-    return u;
-}
-
-uint32_t* unitig_anchors(const kc_ctx* c, const UnitigBufs& u) {
-    uint64_t* b = c->d_unitig_node;
-    return reinterpret_cast<uint32_t*>(b + unitig_layout(u.bound, true, true).anchors);
+    u.verdict = w.verdict ? reinterpret_cast<uint8_t*>(b + l.verdict) : nullptr;
+    return UnitigRanked{u, unitig_rounds(bound), w.anchors ? reinterpret_cast<uint32_t*>(b + l.anchors) : nullptr};
 }
 
 // The ranking on s for up to `bound` nodes (the caller has joined s): the scratch first -- a failure
 // is reported before any kernel of the call is launched -- then the three sweeps and the jump
-// launches.  Leaves the views and the rounds for unitig_write.  with_rec: the record indices of
-// kc_unitig_graph*; with_verdict: the verdict bytes of kc_clean* (kc_api_clean.cpp) and of
-// kc_pop_bubbles* (kc_api_bubble.cpp), whose anchors (with_anchors) lie behind them.
-int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u,
-                int* rounds, bool with_rec, bool with_verdict, bool with_anchors) {
+// launches.  Leaves the views and the rounds for unitig_write and for the filters' kernels
+// (kc_api_filter.cpp).
+int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, UnitigWants w, hipStream_t s,
+                UnitigRanked* r) {
     const uint64_t slots = c->nbuckets * (uint64_t)c->S;
     bound = std::max<uint64_t>(1, std::min(bound, slots));
     if (bound >= UNITIG_MAX_BOUND)
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: " + std::to_string(bound) + " node ids do not fit 32-bit states (the "
                                      "device form sizes by the table's slots, kc_unitigs by the k-mers from min_count on)");
-    const uint64_t words = unitig_layout(bound, with_verdict, with_anchors).words;
+    const uint64_t words = unitig_layout(bound, w).words;
     if (c->d_graph_edges.capacity() < slots || c->d_unitig_ids.capacity() < slots || c->d_unitig_node.capacity() < words ||
-        (with_rec && c->d_unitig_rec.capacity() < bound))
-        make_room(c, unitig_scratch_bytes(slots, bound, with_rec, with_verdict, with_anchors));
+        (w.rec && c->d_unitig_rec.capacity() < bound))
+        make_room(c, unitig_scratch_bytes(slots, bound, w));
     if (!c->d_graph_edges.reserve(slots) || !c->d_unitig_ids.reserve(slots) || !c->d_unitig_node.reserve(words) ||
-        !c->d_unitig_ctl.reserve(UNITIG_CTL_WORDS) || (with_rec && !c->d_unitig_rec.reserve(bound)))
+        !c->d_unitig_ctl.reserve(UNITIG_CTL_WORDS) || (w.rec && !c->d_unitig_rec.reserve(bound)))
         return c->fail(KC_ERR_NOMEM, "kc_unitigs: scratch allocation failed (" +
-                                     std::to_string(unitig_scratch_bytes(slots, bound, with_rec, with_verdict, with_anchors)) + " bytes)");
-    *u = unitig_bufs(c, bound, with_verdict);
-    *rounds = unitig_rounds(bound);
-    HIPCHK(c, hipMemsetAsync(u->ctl, 0, UNITIG_CTL_WORDS * sizeof(unsigned long long), s));
+                                     std::to_string(unitig_scratch_bytes(slots, bound, w)) + " bytes)");
+    *r = unitig_bufs(c, bound, w);
+    HIPCHK(c, hipMemsetAsync(r->u.ctl, 0, UNITIG_CTL_WORDS * sizeof(unsigned long long), s));
     HIPCHK(c, launch_unitig_succ(table_view(c), c->cfg.k, c->cfg.mode == 0 ? 0 : 1, min_count ? min_count : 1, max_count,
-                                 *u, s));
-    HIPCHK(c, launch_unitig_rank(*u, *rounds, s));
+                                 r->u, s));
+    HIPCHK(c, launch_unitig_rank(r->u, r->rounds, s));
     return KC_OK;
 }
 
-// the records, the bases and the statistics of a ranking, each where its pointer is not NULL; rec
+// the records and the bases of a ranking, each where its pointer is not NULL; rec
 // (kc_unitig_graph*): the record indices this launch hands out, per start id
-static int unitig_write(kc_ctx* c, const UnitigBufs& u, int rounds, kc_unitig* recs, uint64_t cap_unitigs, uint8_t* bases,
-                        uint64_t cap_bases, kc_unitig_stats* dev_stats, hipStream_t s, uint32_t* rec = nullptr) {
-    HIPCHK(c, launch_unitig_heads(u, c->cfg.k, rounds, recs, cap_unitigs, bases ? cap_bases : 0, rec, s));
-    if (bases) HIPCHK(c, launch_unitig_emit(table_view(c), c->cfg.k, u, bases, s));
-    if (dev_stats)
-        HIPCHK(c, hipMemcpyAsync(dev_stats, u.ctl + UC_STATS, sizeof(kc_unitig_stats), hipMemcpyDeviceToDevice, s));
+static int unitig_write(kc_ctx* c, const UnitigRanked& r, kc_unitig* recs, uint64_t cap_unitigs, uint8_t* bases,
+                        uint64_t cap_bases, hipStream_t s, uint32_t* rec) {
+    HIPCHK(c, launch_unitig_heads(r.u, c->cfg.k, r.rounds, recs, cap_unitigs, bases ? cap_bases : 0, rec, s));
+    if (bases) HIPCHK(c, launch_unitig_emit(table_view(c), c->cfg.k, r.u, bases, s));
     return KC_OK;
 }
 
@@ -111,103 +106,38 @@ static int unitig_to_host(kc_ctx* c, std::unique_ptr<T, StdFree>* out, const T* 
     return KC_OK;
 }
 
-#pragma GCC visibility pop
-
-extern "C" {
-
-int kc_unitigs_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs, uint64_t cap_unitigs,
-                      uint8_t* bases, uint64_t cap_bases, kc_unitig_stats* stats, void* sp) {
+// The device form of kc_unitigs* and, with_edges, of kc_unitig_graph*, which adds the record index
+// per id to the scratch, the edges' launch and the three statistics words behind kc_unitig_stats.
+static int unitigs_device(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs,
+                          uint64_t cap_unitigs, uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
+                          void* stats, hipStream_t s) {
     if (!c) return KC_ERR_ARG;
     int rc = unitig_check(c, min_count, max_count);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)sp;
+    if (with_edges && ((uintptr_t)edges & 15))
+        return c->fail(KC_ERR_ARG, "kc_unitig_graph_device: dev_edges is not 16-byte aligned");
     if ((rc = flush_host(c))) return rc;
     StreamScope on(c, s);
     if ((rc = on.join())) return rc;
     if ((rc = materialize_zero(c, s))) return rc;  // an emptied table has no unitigs
-    UnitigBufs u;
-    int rounds = 0;
+    UnitigRanked r;
     // no host wait, so the ids are sized by what the host knows: the table's slots
-    if ((rc = unitig_rank(c, min_count, max_count, c->nbuckets * (uint64_t)c->S, s, &u, &rounds))) return rc;
-    if ((rc = unitig_write(c, u, rounds, unitigs, cap_unitigs, bases, cap_bases, stats, s))) return rc;
-    return on.finish();
-}
-
-int kc_unitigs(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
-               kc_unitig_stats* stats) {
-    if (!c) return KC_ERR_ARG;
-    if (unitigs) *unitigs = nullptr;
-    if (bases) *bases = nullptr;
-    int rc = unitig_check(c, min_count, max_count);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    unsigned long long bound = 0;
-    if ((rc = unitig_bound(c, min_count, &bound))) return rc;
-    // rank once, read the totals, allocate, write
-    UnitigBufs u;
-    int rounds = 0;
-    kc_unitig_stats h{};
-    DevBuf<kc_unitig> dr;
-    DevBuf<uint8_t> db;
-    DrainOnError drain{s};
-    if ((rc = unitig_rank(c, min_count, max_count, bound, s, &u, &rounds))) return rc;
-    if ((rc = unitig_write(c, u, rounds, nullptr, 0, nullptr, 0, nullptr, s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(&h, u.ctl + UC_STATS, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    const bool want_r = unitigs && h.unitigs, want_b = bases && h.bases;
-    if (want_r || want_b) {
-        make_room(c, h.unitigs * sizeof(kc_unitig) + h.bases);
-        if ((want_r && !dr.reserve(h.unitigs)) || (want_b && !db.reserve(h.bases)))
-            return c->fail(KC_ERR_NOMEM, "kc_unitigs: record and base buffer allocation failed");
-        if ((rc = unitig_write(c, u, rounds, want_r ? dr.get() : nullptr, h.unitigs, want_b ? db.get() : nullptr, h.bases,
-                               nullptr, s)))
-            return rc;
-    }
-    std::unique_ptr<kc_unitig, StdFree> out_r;
-    std::unique_ptr<uint8_t, StdFree> out_b;
-    if (unitigs) {
-        out_r.reset((kc_unitig*)std::malloc(std::max<size_t>(1, h.unitigs * sizeof(kc_unitig))));
-        if (!out_r) return c->fail(KC_ERR_NOMEM, "host allocation failed");
-        if (want_r) HIPCHK(c, hipMemcpyAsync(out_r.get(), dr, h.unitigs * sizeof(kc_unitig), hipMemcpyDeviceToHost, s));
-    }
-    if (bases) {
-        out_b.reset((uint8_t*)std::malloc(std::max<size_t>(1, h.bases)));
-        if (!out_b) return c->fail(KC_ERR_NOMEM, "host allocation failed");
-        if (want_b) HIPCHK(c, hipMemcpyAsync(out_b.get(), db, h.bases, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(c, hipStreamSynchronize(s));
-    drain.done();
-    if (unitigs) *unitigs = out_r.release();
-    if (bases) *bases = out_b.release();
-    if (stats) *stats = h;
-    return KC_OK;
-}
-
-// ---- the compacted graph: the unitigs and the edges between them (kc_unitig_graph*) -----------------
-int kc_unitig_graph_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs, uint64_t cap_unitigs,
-                           uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
-                           kc_cdbg_stats* stats, void* sp) {
-    if (!c) return KC_ERR_ARG;
-    int rc = unitig_check(c, min_count, max_count);
-    if (rc) return rc;
-    if ((uintptr_t)edges & 15) return c->fail(KC_ERR_ARG, "kc_unitig_graph_device: dev_edges is not 16-byte aligned");
-    hipStream_t s = (hipStream_t)sp;
-    if ((rc = flush_host(c))) return rc;
-    StreamScope on(c, s);
-    if ((rc = on.join())) return rc;
-    if ((rc = materialize_zero(c, s))) return rc;  // an emptied table has no unitigs
-    UnitigBufs u;
-    int rounds = 0;
-    if ((rc = unitig_rank(c, min_count, max_count, c->nbuckets * (uint64_t)c->S, s, &u, &rounds, true))) return rc;
+    if ((rc = unitig_rank(c, min_count, max_count, c->nbuckets * (uint64_t)c->S, with_edges ? UNITIG_GRAPH : UNITIG_PLAIN, s, &r)))
+        return rc;
     // the edges read the record numbering of this heads launch, the one whose records the caller receives
-    if ((rc = unitig_write(c, u, rounds, unitigs, cap_unitigs, bases, cap_bases, nullptr, s, c->d_unitig_rec))) return rc;
-    HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, u, c->d_unitig_rec, edges, cap_edges, s));
-    if (stats) HIPCHK(c, hipMemcpyAsync(stats, u.ctl + UC_STATS, sizeof(kc_cdbg_stats), hipMemcpyDeviceToDevice, s));
+    uint32_t* rec = with_edges ? c->d_unitig_rec.get() : nullptr;
+    if ((rc = unitig_write(c, r, unitigs, cap_unitigs, bases, cap_bases, s, rec))) return rc;
+    if (with_edges) HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, r.u, rec, edges, cap_edges, s));
+    if (stats)
+        HIPCHK(c, hipMemcpyAsync(stats, r.u.ctl + UC_STATS, with_edges ? sizeof(kc_cdbg_stats) : sizeof(kc_unitig_stats),
+                                 hipMemcpyDeviceToDevice, s));
     return on.finish();
 }
 
-int kc_unitig_graph(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
-                    kc_unitig_edge** edges, kc_cdbg_stats* stats) {
+// The host form of kc_unitigs* and, with_edges, of kc_unitig_graph*: rank once, read the totals
+// (records and edges counted without buffers), allocate, write.
+static int unitigs_host(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+                        kc_unitig_edge** edges, void* stats) {
     if (!c) return KC_ERR_ARG;
     if (unitigs) *unitigs = nullptr;
     if (bases) *bases = nullptr;
@@ -217,30 +147,29 @@ int kc_unitig_graph(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig
     hipStream_t s = c->stream;
     unsigned long long bound = 0;
     if ((rc = unitig_bound(c, min_count, &bound))) return rc;
-    // rank once, read the totals (records and edges counted without buffers), allocate, write
-    UnitigBufs u;
-    int rounds = 0;
-    kc_cdbg_stats h{};
+    UnitigRanked r;
+    kc_cdbg_stats h{};  // (kc_unitigs: its first five words)
+    const size_t stat_bytes = with_edges ? sizeof(kc_cdbg_stats) : sizeof(kc_unitig_stats);
     DevBuf<kc_unitig> dr;
     DevBuf<uint8_t> db;
     DevBuf<kc_unitig_edge> de;
     DrainOnError drain{s};
-    if ((rc = unitig_rank(c, min_count, max_count, bound, s, &u, &rounds, true))) return rc;
-    uint32_t* rec = c->d_unitig_rec;
-    if ((rc = unitig_write(c, u, rounds, nullptr, 0, nullptr, 0, nullptr, s, rec))) return rc;
-    HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, u, rec, nullptr, 0, s));
-    HIPCHK(c, hipMemcpyAsync(&h, u.ctl + UC_STATS, sizeof(h), hipMemcpyDeviceToHost, s));
+    if ((rc = unitig_rank(c, min_count, max_count, bound, with_edges ? UNITIG_GRAPH : UNITIG_PLAIN, s, &r))) return rc;
+    uint32_t* rec = with_edges ? c->d_unitig_rec.get() : nullptr;
+    if ((rc = unitig_write(c, r, nullptr, 0, nullptr, 0, s, rec))) return rc;
+    if (with_edges) HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, r.u, rec, nullptr, 0, s));
+    HIPCHK(c, hipMemcpyAsync(&h, r.u.ctl + UC_STATS, stat_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     const bool want_r = unitigs && h.unitigs, want_b = bases && h.bases, want_e = edges && h.edges;
     if (want_r || want_b || want_e) {
         make_room(c, h.unitigs * sizeof(kc_unitig) + h.bases + h.edges * sizeof(kc_unitig_edge));
         if ((want_r && !dr.reserve(h.unitigs)) || (want_b && !db.reserve(h.bases)) || (want_e && !de.reserve(h.edges)))
-            return c->fail(KC_ERR_NOMEM, "kc_unitig_graph: record, base and edge buffer allocation failed");
+            return c->fail(KC_ERR_NOMEM, with_edges ? "kc_unitig_graph: record, base and edge buffer allocation failed"
+                                                    : "kc_unitigs: record and base buffer allocation failed");
         // the records' launch numbers them anew, and the edges after it read that numbering
-        if ((rc = unitig_write(c, u, rounds, want_r ? dr.get() : nullptr, h.unitigs, want_b ? db.get() : nullptr, h.bases,
-                               nullptr, s, rec)))
+        if ((rc = unitig_write(c, r, want_r ? dr.get() : nullptr, h.unitigs, want_b ? db.get() : nullptr, h.bases, s, rec)))
             return rc;
-        if (want_e) HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, u, rec, de.get(), h.edges, s));
+        if (want_e) HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, r.u, rec, de.get(), h.edges, s));
     }
     std::unique_ptr<kc_unitig, StdFree> out_r;
     std::unique_ptr<uint8_t, StdFree> out_b;
@@ -253,8 +182,36 @@ int kc_unitig_graph(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig
     if (unitigs) *unitigs = out_r.release();
     if (bases) *bases = out_b.release();
     if (edges) *edges = out_e.release();
-    if (stats) *stats = h;
+    if (stats) std::memcpy(stats, &h, stat_bytes);
     return KC_OK;
+}
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int kc_unitigs_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs, uint64_t cap_unitigs,
+                      uint8_t* bases, uint64_t cap_bases, kc_unitig_stats* stats, void* sp) {
+    return unitigs_device(c, false, min_count, max_count, unitigs, cap_unitigs, bases, cap_bases, nullptr, 0, stats,
+                          (hipStream_t)sp);
+}
+
+int kc_unitigs(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+               kc_unitig_stats* stats) {
+    return unitigs_host(c, false, min_count, max_count, unitigs, bases, nullptr, stats);
+}
+
+// ---- the compacted graph: the unitigs and the edges between them (kc_unitig_graph*) -----------------
+int kc_unitig_graph_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs, uint64_t cap_unitigs,
+                           uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
+                           kc_cdbg_stats* stats, void* sp) {
+    return unitigs_device(c, true, min_count, max_count, unitigs, cap_unitigs, bases, cap_bases, edges, cap_edges, stats,
+                          (hipStream_t)sp);
+}
+
+int kc_unitig_graph(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+                    kc_unitig_edge** edges, kc_cdbg_stats* stats) {
+    return unitigs_host(c, true, min_count, max_count, unitigs, bases, edges, stats);
 }
 
 }  // extern "C"

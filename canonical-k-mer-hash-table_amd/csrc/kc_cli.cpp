@@ -38,6 +38,14 @@ namespace {
 
 enum CliExit { kConversion = 104, kValidation = 105, kRequired = 106, kRequires = 107, kExcludes = 108, kExtras = 109 };
 
+// the six options --clean-* and --pop-* both have: --X-max-mean, --X-rounds, --X-min, --X-max,
+// --X-out, --X-stats (take_filter_opt, check_filter_opts)
+struct FilterOpts {
+    unsigned long long max_mean = 0, rounds = 1, min = 0, max = 0;
+    bool dep_set = false, min_set = false;  // an option that needs the family's switch was given; --X-min was
+    std::string out, stats;
+};
+
 struct Args {
     std::string input, output;
     long long k = 0;
@@ -101,17 +109,17 @@ struct Args {
     // table into a new one, R rounds at the most, which --graph, --unitigs and --gfa then read (their
     // own ranges applied to it); every other output still reads the counted table.  The range as for
     // --graph.
-    unsigned long long clean_tips = 0, clean_iso = 0, clean_max_mean = 0, clean_rounds = 1, clean_min = 0, clean_max = 0;
-    bool clean_tips_set = false, clean_iso_set = false, clean_dep_set = false, clean_min_set = false;
-    std::string clean_out, clean_stats;
+    unsigned long long clean_tips = 0, clean_iso = 0;
+    bool clean_tips_set = false, clean_iso_set = false;
+    FilterOpts clean;
     bool cleaning() const { return clean_tips_set || clean_iso_set; }
     // --pop-bubbles N [--pop-max-diff D] [--pop-max-mean M] [--pop-rounds R] [--pop-min N] [--pop-max N]
     // [--pop-out FILE] [--pop-stats FILE]: bubble popping (kc_pop_bubbles) of the counted table -- of
     // the cleaned one when --clean-* are given too -- into a new one, R rounds at the most, which
     // --graph, --unitigs and --gfa then read.  The range as for --clean-min / --clean-max.
-    unsigned long long pop_nodes = 0, pop_max_diff = 0, pop_max_mean = 0, pop_rounds = 1, pop_min = 0, pop_max = 0;
-    bool pop_set = false, pop_dep_set = false, pop_min_set = false;
-    std::string pop_out, pop_stats;
+    unsigned long long pop_nodes = 0, pop_max_diff = 0;
+    bool pop_set = false;
+    FilterOpts pop;
 };
 
 const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
@@ -221,6 +229,33 @@ bool parse_double(const std::string& s, double* v) {
     char* end = nullptr;
     *v = std::strtod(s.c_str(), &end);
     return end && *end == 0;
+}
+
+// o = v as one of FilterOpts' six under `prefix` ("--clean-", "--pop-"): 1 taken, 0 not one of them,
+// -1 one of them whose value is no 32-bit number
+int take_filter_opt(FilterOpts* f, const std::string& prefix, const std::string& o, const std::string& v) {
+    const std::string name = o.compare(0, prefix.size(), prefix) == 0 ? o.substr(prefix.size()) : "";
+    unsigned long long* num = name == "max-mean" ? &f->max_mean : name == "rounds" ? &f->rounds
+                              : name == "min"    ? &f->min : name == "max" ? &f->max : nullptr;
+    std::string* text = name == "out" ? &f->out : name == "stats" ? &f->stats : nullptr;
+    if (!num && !text) return 0;
+    if (num && (!parse_uint(v, num) || *num > 0xFFFFFFFFull)) return -1;
+    if (text) *text = v;
+    f->dep_set = true;
+    f->min_set |= name == "min";
+    return 1;
+}
+
+// What both families check once all options are read (on: the family's switch was given); the
+// range's default as for --graph-min.  -1: fine, else the exit code.
+int check_filter_opts(FilterOpts* f, bool on, const std::string& prefix, const Args& a, const char* requires_text,
+                      const char* excludes_text) {
+    if (f->dep_set && !on) return cli_error(kRequires, requires_text);
+    if (!f->min_set) f->min = std::min<unsigned long long>(a.min_abundance, 0xFFFFFFFFull);
+    if (f->max && f->min > f->max) return cli_error(kValidation, prefix + "min: a minimum above its maximum");
+    if (f->rounds < 1) return cli_error(kValidation, prefix + "rounds: Value 0 not in range 1 to inf");
+    if (on && !a.op_name.empty()) return cli_error(kExcludes, excludes_text);
+    return -1;
 }
 
 // BGZF input (blocked gzip, bgzip / htslib: every member carries its compressed size in a
@@ -407,41 +442,15 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 (o == "--gfa-min" ? a->gfa_min : a->gfa_max) = u;
                 (o == "--gfa-min" ? a->gfa_min_set : a->gfa_max_set) = true;
-            } else if (o == "--clean-tips" || o == "--clean-isolated" || o == "--clean-max-mean" || o == "--clean-rounds" ||
-                       o == "--clean-min" || o == "--clean-max") {
+            } else if (int t = take_filter_opt(&a->clean, "--clean-", o, v) | take_filter_opt(&a->pop, "--pop-", o, v)) {
+                if (t < 0) return cli_error(kConversion, "Could not convert: " + o + " = " + v);  // (the other call gave 0)
+            } else if (o == "--clean-tips" || o == "--clean-isolated" || o == "--pop-bubbles" || o == "--pop-max-diff") {
                 if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
-                if (o == "--clean-tips") {
-                    a->clean_tips = u;
-                    a->clean_tips_set = true;
-                } else if (o == "--clean-isolated") {
-                    a->clean_iso = u;
-                    a->clean_iso_set = true;
-                } else {
-                    (o == "--clean-max-mean" ? a->clean_max_mean : o == "--clean-rounds" ? a->clean_rounds
-                     : o == "--clean-min"    ? a->clean_min : a->clean_max) = u;
-                    a->clean_dep_set = true;
-                    if (o == "--clean-min") a->clean_min_set = true;
-                }
-            } else if (o == "--clean-out" || o == "--clean-stats") {
-                (o == "--clean-out" ? a->clean_out : a->clean_stats) = v;
-                a->clean_dep_set = true;
-            } else if (o == "--pop-bubbles" || o == "--pop-max-diff" || o == "--pop-max-mean" || o == "--pop-rounds" ||
-                       o == "--pop-min" || o == "--pop-max") {
-                if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
-                    return cli_error(kConversion, "Could not convert: " + o + " = " + v);
-                if (o == "--pop-bubbles") {
-                    a->pop_nodes = u;
-                    a->pop_set = true;
-                } else {
-                    (o == "--pop-max-diff" ? a->pop_max_diff : o == "--pop-max-mean" ? a->pop_max_mean
-                     : o == "--pop-rounds" ? a->pop_rounds : o == "--pop-min" ? a->pop_min : a->pop_max) = u;
-                    a->pop_dep_set = true;
-                    if (o == "--pop-min") a->pop_min_set = true;
-                }
-            } else if (o == "--pop-out" || o == "--pop-stats") {
-                (o == "--pop-out" ? a->pop_out : a->pop_stats) = v;
-                a->pop_dep_set = true;
+                (o == "--clean-tips" ? a->clean_tips : o == "--clean-isolated" ? a->clean_iso
+                 : o == "--pop-bubbles" ? a->pop_nodes : a->pop_max_diff) = u;
+                (o == "--clean-tips" ? a->clean_tips_set : o == "--clean-isolated" ? a->clean_iso_set
+                 : o == "--pop-bubbles" ? a->pop_set : a->pop.dep_set) = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -506,21 +515,14 @@ int parse(int argc, char** argv, Args* a) {
         return cli_error(kRequires, "--gfa-min/--gfa-max require --gfa");
     if (!a->gfa_min_set) a->gfa_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
     if (a->gfa_max && a->gfa_min > a->gfa_max) return cli_error(kValidation, "--gfa-min: a minimum above its maximum");
-    if (a->clean_dep_set && !a->cleaning())
-        return cli_error(kRequires, "--clean-max-mean/--clean-rounds/--clean-min/--clean-max/--clean-out/--clean-stats "
-                                    "require --clean-tips or --clean-isolated");
-    if (!a->clean_min_set) a->clean_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
-    if (a->clean_max && a->clean_min > a->clean_max)
-        return cli_error(kValidation, "--clean-min: a minimum above its maximum");
-    if (a->clean_rounds < 1) return cli_error(kValidation, "--clean-rounds: Value 0 not in range 1 to inf");
-    if (a->cleaning() && !a->op_name.empty()) return cli_error(kExcludes, "--clean-tips/--clean-isolated exclude --op");
-    if (a->pop_dep_set && !a->pop_set)
-        return cli_error(kRequires, "--pop-max-diff/--pop-max-mean/--pop-rounds/--pop-min/--pop-max/--pop-out/--pop-stats "
-                                    "require --pop-bubbles");
-    if (!a->pop_min_set) a->pop_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
-    if (a->pop_max && a->pop_min > a->pop_max) return cli_error(kValidation, "--pop-min: a minimum above its maximum");
-    if (a->pop_rounds < 1) return cli_error(kValidation, "--pop-rounds: Value 0 not in range 1 to inf");
-    if (a->pop_set && !a->op_name.empty()) return cli_error(kExcludes, "--pop-bubbles excludes --op");
+    int bad = check_filter_opts(&a->clean, a->cleaning(), "--clean-", *a,
+                                "--clean-max-mean/--clean-rounds/--clean-min/--clean-max/--clean-out/--clean-stats "
+                                "require --clean-tips or --clean-isolated", "--clean-tips/--clean-isolated exclude --op");
+    if (bad >= 0) return bad;
+    bad = check_filter_opts(&a->pop, a->pop_set, "--pop-", *a,
+                            "--pop-max-diff/--pop-max-mean/--pop-rounds/--pop-min/--pop-max/--pop-out/--pop-stats "
+                            "require --pop-bubbles", "--pop-bubbles excludes --op");
+    if (bad >= 0) return bad;
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -1376,126 +1378,116 @@ int main(int argc, char** argv) {
         std::cout << "Corrected " << bases << " bases in " << recs << " of " << nrec << " records (" << cands
                   << " candidates, " << ambig << " ambiguous, " << dropped << " dropped)\n";
     }
-    // --clean-tips / --clean-isolated (extension): up to --clean-rounds rounds of graph cleaning, each
-    // into a new table sized from a statistics-only call -- no Bloom filter, every k-mer of it output
-    // (-a 1) -- which the three graph outputs below read instead of the counted table
+    // --clean-tips / --clean-isolated and --pop-bubbles (extensions): up to --X-rounds rounds of a graph
+    // filter, each into a new table sized from a statistics-only call -- no Bloom filter, every k-mer
+    // of it output (-a 1) -- which the three graph outputs below read instead of the counted table
     kc_ctx* gctx = ctx;
-    auto gdie = [&](const char* what) {
-        std::cerr << what << ": " << kc_last_error(gctx) << std::endl;
+    auto quit = [&] {
         if (gctx != ctx) kc_destroy(gctx);
         kc_destroy(ctx);
-        std::exit(1);
+        return 1;
+    };
+    auto gdie = [&](const char* what) {
+        std::cerr << what << ": " << kc_last_error(gctx) << std::endl;
+        std::exit(quit());
+    };
+    // call(dst or nullptr, src, st): the filter; line, say: a round's stats-file and stdout lines; done:
+    // the round removed nothing.  false: an error has been reported.
+    auto filter_rounds = [&](const FilterOpts& o, const char* what, const char* writing, auto* st, auto call, auto line,
+                             auto say, auto done) -> bool {
+        auto fail = [](const std::string& where, kc_ctx* of) {
+            std::cerr << where << ": " << kc_last_error(of) << std::endl;
+            return false;
+        };
+        FILE* sf = nullptr;
+        if (!o.stats.empty() && !(sf = std::fopen(o.stats.c_str(), "w"))) {
+            std::cerr << "cannot write " << o.stats << std::endl;
+            return false;
+        }
+        for (unsigned long long round = 1; round <= o.rounds; round++) {
+            if (call(nullptr, gctx, st) != KC_OK) return fail(what, gctx);
+            kc_config rcfg = cfg;
+            rcfg.bf_enable = 0;
+            rcfg.est_unique = 0;
+            rcfg.min_abundance = 1;
+            rcfg.table_slots = st->out_keys + st->out_keys / 8 + 4096;
+            rcfg.batch_bytes = 1 << 20;  // (nothing is staged into it)
+            kc_ctx* next = nullptr;
+            if (kc_create(&rcfg, &next) != KC_OK) return fail(std::string("kc_create (") + what + ")", nullptr);
+            kc_stats str;
+            if (call(next, gctx, st) != KC_OK || kc_finish(next, &str) != KC_OK) {
+                fail(what, next);
+                kc_destroy(next);
+                return false;
+            }
+            if (gctx != ctx) kc_destroy(gctx);
+            gctx = next;
+            if (sf) line(sf, round, *st);
+            say(round, *st, str.table_slots);
+            if (done(*st)) break;
+        }
+        if (sf && std::fclose(sf) != 0) {
+            std::cerr << "cannot write " << o.stats << std::endl;
+            return fail(what, gctx);
+        }
+        if (!o.out.empty() && kc_write(gctx, o.out.c_str()) != KC_OK) return fail(writing, gctx);
+        return true;
     };
     if (a.cleaning()) {
-        FILE* sf = nullptr;
-        if (!a.clean_stats.empty() && !(sf = std::fopen(a.clean_stats.c_str(), "w"))) {
-            std::cerr << "cannot write " << a.clean_stats << std::endl;
-            kc_destroy(ctx);
-            return 1;
-        }
         kc_clean_desc cd;
         std::memset(&cd, 0, sizeof cd);
-        cd.min_count = (uint32_t)a.clean_min;
-        cd.max_count = (uint32_t)a.clean_max;
+        cd.min_count = (uint32_t)a.clean.min;
+        cd.max_count = (uint32_t)a.clean.max;
         cd.tip_max_nodes = (uint32_t)a.clean_tips;
         cd.iso_max_nodes = (uint32_t)a.clean_iso;
-        cd.max_mean = (uint32_t)a.clean_max_mean;
-        for (unsigned long long round = 1; round <= a.clean_rounds; round++) {
-            kc_clean_stats cs;
-            if (kc_clean(nullptr, gctx, &cd, &cs) != KC_OK) gdie("graph cleaning");
-            kc_config rcfg = cfg;
-            rcfg.bf_enable = 0;
-            rcfg.est_unique = 0;
-            rcfg.min_abundance = 1;
-            rcfg.table_slots = cs.out_keys + cs.out_keys / 8 + 4096;
-            rcfg.batch_bytes = 1 << 20;  // (nothing is staged into it)
-            kc_ctx* next = nullptr;
-            if (kc_create(&rcfg, &next) != KC_OK) {
-                std::cerr << "kc_create (graph cleaning): " << kc_last_error(nullptr) << std::endl;
-                if (gctx != ctx) kc_destroy(gctx);
-                kc_destroy(ctx);
-                return 1;
-            }
-            kc_stats str;
-            if (kc_clean(next, gctx, &cd, &cs) != KC_OK || kc_finish(next, &str) != KC_OK) {
-                std::cerr << "graph cleaning: " << kc_last_error(next) << std::endl;
-                kc_destroy(next);
-                if (gctx != ctx) kc_destroy(gctx);
-                kc_destroy(ctx);
-                return 1;
-            }
-            if (gctx != ctx) kc_destroy(gctx);
-            gctx = next;
-            if (sf)
-                std::fprintf(sf, "round %llu unitigs %llu nodes %llu tips %llu tip_nodes %llu isolated %llu isolated_nodes %llu "
-                                 "out_keys %llu out_sum %llu\n", round, (unsigned long long)cs.unitigs,
-                             (unsigned long long)cs.nodes, (unsigned long long)cs.tips, (unsigned long long)cs.tip_nodes,
-                             (unsigned long long)cs.isolated, (unsigned long long)cs.isolated_nodes,
-                             (unsigned long long)cs.out_keys, (unsigned long long)cs.out_sum);
-            std::cout << "Graph cleaning round " << round << ": " << cs.unitigs << " unitigs, " << cs.nodes << " nodes; removed "
-                      << cs.tips << " tips (" << cs.tip_nodes << " nodes) and " << cs.isolated << " isolated unitigs ("
-                      << cs.isolated_nodes << " nodes); kept " << cs.out_keys << " k-mers in " << str.table_slots << " slots\n";
-            if (!cs.tips && !cs.isolated) break;
-        }
-        if (sf && std::fclose(sf) != 0) { std::cerr << "cannot write " << a.clean_stats << std::endl; gdie("graph cleaning"); }
-        if (!a.clean_out.empty() && kc_write(gctx, a.clean_out.c_str()) != KC_OK) gdie("writing the cleaned k-mers");
+        cd.max_mean = (uint32_t)a.clean.max_mean;
+        kc_clean_stats cs;
+        if (!filter_rounds(
+                a.clean, "graph cleaning", "writing the cleaned k-mers", &cs,
+                [&](kc_ctx* dst, kc_ctx* src, kc_clean_stats* st) { return kc_clean(dst, src, &cd, st); },
+                [](FILE* sf, unsigned long long round, const kc_clean_stats& cs) {
+                    std::fprintf(sf, "round %llu unitigs %llu nodes %llu tips %llu tip_nodes %llu isolated %llu isolated_nodes %llu "
+                                     "out_keys %llu out_sum %llu\n", round, (unsigned long long)cs.unitigs,
+                                 (unsigned long long)cs.nodes, (unsigned long long)cs.tips, (unsigned long long)cs.tip_nodes,
+                                 (unsigned long long)cs.isolated, (unsigned long long)cs.isolated_nodes,
+                                 (unsigned long long)cs.out_keys, (unsigned long long)cs.out_sum);
+                },
+                [](unsigned long long round, const kc_clean_stats& cs, auto slots) {
+                    std::cout << "Graph cleaning round " << round << ": " << cs.unitigs << " unitigs, " << cs.nodes
+                              << " nodes; removed " << cs.tips << " tips (" << cs.tip_nodes << " nodes) and " << cs.isolated
+                              << " isolated unitigs (" << cs.isolated_nodes << " nodes); kept " << cs.out_keys << " k-mers in "
+                              << slots << " slots\n";
+                },
+                [](const kc_clean_stats& cs) { return !cs.tips && !cs.isolated; }))
+            return quit();
     }
-    // --pop-bubbles (extension): up to --pop-rounds rounds of bubble popping on the table the cleaning
-    // left (or the counted one), each into a new table as above
+    // (--pop-bubbles reads the table the cleaning left, or the counted one)
     if (a.pop_set) {
-        FILE* sf = nullptr;
-        if (!a.pop_stats.empty() && !(sf = std::fopen(a.pop_stats.c_str(), "w"))) {
-            std::cerr << "cannot write " << a.pop_stats << std::endl;
-            if (gctx != ctx) kc_destroy(gctx);
-            kc_destroy(ctx);
-            return 1;
-        }
         kc_bubble_desc bd;
         std::memset(&bd, 0, sizeof bd);
-        bd.min_count = (uint32_t)a.pop_min;
-        bd.max_count = (uint32_t)a.pop_max;
+        bd.min_count = (uint32_t)a.pop.min;
+        bd.max_count = (uint32_t)a.pop.max;
         bd.max_nodes = (uint32_t)a.pop_nodes;
         bd.max_diff = (uint32_t)a.pop_max_diff;
-        bd.max_mean = (uint32_t)a.pop_max_mean;
-        for (unsigned long long round = 1; round <= a.pop_rounds; round++) {
-            kc_bubble_stats bs;
-            if (kc_pop_bubbles(nullptr, gctx, &bd, &bs) != KC_OK) gdie("bubble popping");
-            kc_config rcfg = cfg;
-            rcfg.bf_enable = 0;
-            rcfg.est_unique = 0;
-            rcfg.min_abundance = 1;
-            rcfg.table_slots = bs.out_keys + bs.out_keys / 8 + 4096;
-            rcfg.batch_bytes = 1 << 20;  // (nothing is staged into it)
-            kc_ctx* next = nullptr;
-            if (kc_create(&rcfg, &next) != KC_OK) {
-                std::cerr << "kc_create (bubble popping): " << kc_last_error(nullptr) << std::endl;
-                if (gctx != ctx) kc_destroy(gctx);
-                kc_destroy(ctx);
-                return 1;
-            }
-            kc_stats str;
-            if (kc_pop_bubbles(next, gctx, &bd, &bs) != KC_OK || kc_finish(next, &str) != KC_OK) {
-                std::cerr << "bubble popping: " << kc_last_error(next) << std::endl;
-                kc_destroy(next);
-                if (gctx != ctx) kc_destroy(gctx);
-                kc_destroy(ctx);
-                return 1;
-            }
-            if (gctx != ctx) kc_destroy(gctx);
-            gctx = next;
-            if (sf)
-                std::fprintf(sf, "round %llu unitigs %llu nodes %llu branches %llu parallel %llu popped %llu popped_nodes %llu "
-                                 "out_keys %llu out_sum %llu\n", round, (unsigned long long)bs.unitigs,
-                             (unsigned long long)bs.nodes, (unsigned long long)bs.branches, (unsigned long long)bs.parallel,
-                             (unsigned long long)bs.popped, (unsigned long long)bs.popped_nodes,
-                             (unsigned long long)bs.out_keys, (unsigned long long)bs.out_sum);
-            std::cout << "Bubble popping round " << round << ": " << bs.unitigs << " unitigs, " << bs.nodes << " nodes, "
-                      << bs.branches << " branches, " << bs.parallel << " of them parallel; popped " << bs.popped << " ("
-                      << bs.popped_nodes << " nodes); kept " << bs.out_keys << " k-mers in " << str.table_slots << " slots\n";
-            if (!bs.popped) break;
-        }
-        if (sf && std::fclose(sf) != 0) { std::cerr << "cannot write " << a.pop_stats << std::endl; gdie("bubble popping"); }
-        if (!a.pop_out.empty() && kc_write(gctx, a.pop_out.c_str()) != KC_OK) gdie("writing the popped k-mers");
+        bd.max_mean = (uint32_t)a.pop.max_mean;
+        kc_bubble_stats bs;
+        if (!filter_rounds(
+                a.pop, "bubble popping", "writing the popped k-mers", &bs,
+                [&](kc_ctx* dst, kc_ctx* src, kc_bubble_stats* st) { return kc_pop_bubbles(dst, src, &bd, st); },
+                [](FILE* sf, unsigned long long round, const kc_bubble_stats& bs) {
+                    std::fprintf(sf, "round %llu unitigs %llu nodes %llu branches %llu parallel %llu popped %llu popped_nodes %llu "
+                                     "out_keys %llu out_sum %llu\n", round, (unsigned long long)bs.unitigs,
+                                 (unsigned long long)bs.nodes, (unsigned long long)bs.branches, (unsigned long long)bs.parallel,
+                                 (unsigned long long)bs.popped, (unsigned long long)bs.popped_nodes,
+                                 (unsigned long long)bs.out_keys, (unsigned long long)bs.out_sum);
+                },
+                [](unsigned long long round, const kc_bubble_stats& bs, auto slots) {
+                    std::cout << "Bubble popping round " << round << ": " << bs.unitigs << " unitigs, " << bs.nodes << " nodes, "
+                              << bs.branches << " branches, " << bs.parallel << " of them parallel; popped " << bs.popped << " ("
+                              << bs.popped_nodes << " nodes); kept " << bs.out_keys << " k-mers in " << slots << " slots\n";
+                },
+                [](const kc_bubble_stats& bs) { return !bs.popped; }))
+            return quit();
     }
     if (!a.graph.empty() || !a.graph_stats.empty()) {  // extension: the de Bruijn graph of the counted (or cleaned, popped) k-mers
         uint64_t* grec = nullptr;

@@ -451,15 +451,18 @@ bool use_partitioned_bloom(const kc_ctx* c, uint64_t syms);
 int sync_for_read(kc_ctx* c);
 void make_room(kc_ctx* c, uint64_t bytes);
 void drop_compact(kc_ctx* c);
-// kc_api_unitig.cpp (shared with kc_api_clean.cpp and kc_api_bubble.cpp: the checks, the ids' bound of
-// a host form, the ranking)
-UnitigBufs unitig_bufs(const kc_ctx* c, uint64_t bound, bool with_verdict = false);
+// kc_api_unitig.cpp (shared with kc_api_filter.cpp: the checks, the ids' bound of a host form, the
+// ranking).  A ranking leaves the views of the context's scratch, the jump rounds the later launches
+// repeat, and the anchors behind the verdict bytes (nullptr unless wanted)
+struct UnitigRanked {
+    UnitigBufs u;
+    int rounds;
+    uint32_t* anchors;
+};
 int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count);
 int unitig_bound(kc_ctx* c, uint32_t min_count, unsigned long long* bound);
-int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, hipStream_t s, UnitigBufs* u, int* rounds,
-                bool with_rec = false, bool with_verdict = false, bool with_anchors = false);
-// the anchors of kc_pop_bubbles* in the scratch a ranking with_verdict and with_anchors left (u.bound ids)
-uint32_t* unitig_anchors(const kc_ctx* c, const UnitigBufs& u);
+int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, UnitigWants w, hipStream_t s,
+                UnitigRanked* r);
 // kc_api_pass.cpp
 int flush_host(kc_ctx* c);
 int device_pass(kc_ctx* c, const uint8_t* img, const kc_chunk* chunks, size_t n, int fmt, int pass, hipStream_t s);
@@ -483,6 +486,41 @@ int insert_on(kc_ctx* c, StreamScope& on, bool bloom, bool prof_first, Size size
         c->table_fresh = c->table_zero_pending = false;
     }
     return on.finish();
+}
+
+// ---- what every call on two or three contexts shares (kc_api_join.cpp, kc_api_filter.cpp) ----------
+// The error of a step on `from` is reported on the context the caller reads: dst, else the first operand.
+inline int route_rc(kc_ctx* err, kc_ctx* from, int rc) {
+    if (rc && from != err) err->err = from->err;
+    return rc;
+}
+
+// The write into dst on s: dst's host-side state as after kc_insert_counts_device's direct insert
+// (the compact representation is a snapshot of the table before this call, so it goes), dst zeroed
+// if that is pending, then `work`, the launches that insert.  Without a dst, `work` alone.
+template <class Work>
+int write_dst(kc_ctx* dst, hipStream_t s, Work work) {
+    if (!dst) return work();
+    if (dst->d_cwords) drop_compact(dst);
+    StreamScope on_d(dst, s);
+    return insert_on(dst, on_d, false, true, [&] { return materialize_zero(dst, s); }, work);
+}
+
+// The host form of a call whose only output is a statistics struct: body(device struct or nullptr,
+// stream) is the device form, on the stream of the context that reports the error; then the copy
+// back and the wait -- also after an error, since the kernels may still write the struct.
+template <class Stats, class Body>
+int stats_host_form(kc_ctx* err, const char* name, Stats* stats, Body body) {
+    DevBuf<Stats> d;
+    if (stats && !d.reserve(1)) return err->fail(KC_ERR_NOMEM, std::string(name) + ": statistics allocation failed");
+    hipStream_t s = err->stream;
+    int rc = body(d.get(), s);
+    hipError_t e = hipSuccess;
+    if (rc == KC_OK && stats) e = hipMemcpyAsync(stats, d, sizeof(Stats), hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (rc == KC_OK && (e != hipSuccess || e2 != hipSuccess))
+        rc = err->hipfail(e != hipSuccess ? e : e2, (std::string(name) + ": statistics copy").c_str());
+    return rc;
 }
 
 #pragma GCC visibility pop

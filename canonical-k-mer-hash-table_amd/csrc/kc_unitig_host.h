@@ -30,12 +30,20 @@ inline int unitig_rounds(uint64_t bound) {
     return lg + 1;
 }
 
-// the scratch of a call (with_rec: of kc_unitig_graph*, with_verdict: of kc_clean* and
-// kc_pop_bubbles*, with_anchors: of kc_pop_bubbles*), control words aside; 0: it overflows 64 bits
-inline uint64_t unitig_scratch_bytes(uint64_t table_slots, uint64_t bound, bool with_rec = false,
-                                     bool with_verdict = false, bool with_anchors = false) {
-    const uint64_t node = UNITIG_NODE_BYTES + (with_rec ? UNITIG_REC_BYTES : 0) + (with_verdict ? UNITIG_VERDICT_BYTES : 0) +
-                          (with_anchors ? UNITIG_ANCHOR_BYTES : 0);
+// What a ranking is asked for on top of the per-node arrays every call has: rec, the record index
+// of the unitig that starts at the node id (kc_unitig_graph*); verdict, its verdict byte (kc_clean*,
+// kc_pop_bubbles*); anchors, its two anchors (kc_pop_bubbles*).  The calls name theirs here, so that
+// no call site spells out three booleans.
+struct UnitigWants {
+    bool rec = false, verdict = false, anchors = false;
+};
+constexpr UnitigWants UNITIG_PLAIN{}, UNITIG_GRAPH{true, false, false}, UNITIG_CLEAN{false, true, false},
+    UNITIG_BUBBLE{false, true, true};
+
+// the scratch of a call, control words aside; 0: it overflows 64 bits
+inline uint64_t unitig_scratch_bytes(uint64_t table_slots, uint64_t bound, UnitigWants w = UNITIG_PLAIN) {
+    const uint64_t node = UNITIG_NODE_BYTES + (w.rec ? UNITIG_REC_BYTES : 0) + (w.verdict ? UNITIG_VERDICT_BYTES : 0) +
+                          (w.anchors ? UNITIG_ANCHOR_BYTES : 0);
     if (table_slots > ~0ULL / UNITIG_SLOT_BYTES || bound > ~0ULL / node) return 0;
     const uint64_t a = table_slots * UNITIG_SLOT_BYTES, b = bound * node;
     return a + b < a ? 0 : a + b;
@@ -43,14 +51,14 @@ inline uint64_t unitig_scratch_bytes(uint64_t table_slots, uint64_t bound, bool 
 
 // The per-node arrays in one block of 64-bit words, the widest first so that each is aligned:
 // offsets in words of the two state buffers (6 words a node each), slot_of, off (2), succ (1), then
-// the three 32-bit arrays tc, start and pos (half a word a node, rounded up) and, with_verdict
-// (kc_clean* and kc_pop_bubbles*), the verdict bytes (an eighth of a word a node, rounded up) behind
-// them, and, with_anchors (kc_pop_bubbles* only), two 32-bit anchors a node (one word) behind those:
-// the other calls' offsets and words are the same with or without
+// the three 32-bit arrays tc, start and pos (half a word a node, rounded up) and, where wanted, the
+// verdict bytes (an eighth of a word a node, rounded up) behind them and two 32-bit anchors a node
+// (one word) behind those: every other offset is the same with or without (the record indices of
+// UnitigWants::rec are a buffer of their own)
 struct UnitigLayout {
     uint64_t st0, st1, slot_of, off, succ, tc, start, pos, verdict, anchors, words;
 };
-inline UnitigLayout unitig_layout(uint64_t bound, bool with_verdict = false, bool with_anchors = false) {
+inline UnitigLayout unitig_layout(uint64_t bound, UnitigWants w = UNITIG_PLAIN) {
     const uint64_t half = (bound + 1) / 2;
     UnitigLayout l;
     l.st0 = 0;
@@ -62,8 +70,8 @@ inline UnitigLayout unitig_layout(uint64_t bound, bool with_verdict = false, boo
     l.start = l.tc + half;
     l.pos = l.start + half;
     l.verdict = l.pos + half;
-    l.anchors = l.verdict + (with_verdict ? (bound + 7) / 8 : 0);
-    l.words = l.anchors + (with_anchors ? bound : 0);
+    l.anchors = l.verdict + (w.verdict ? (bound + 7) / 8 : 0);
+    l.words = l.anchors + (w.anchors ? bound : 0);
     return l;
 }
 

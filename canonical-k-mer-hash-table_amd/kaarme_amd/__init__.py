@@ -1110,6 +1110,33 @@ def table_compare(a: KmerCounter, b: KmerCounter, a_range=(1, 0), b_range=(1, 0)
     return r
 
 
+def _filter_rounds(name, src, rounds, stats_only, into, done, rule) -> Tuple[KmerCounter, List[dict]]:
+    """The round driver of clean_rounds and pop_rounds: stats_only(cur, **rule) sizes the next table,
+    into(dst, cur, **rule) fills it, done(statistics) ends the rounds early."""
+    if rounds < 1:
+        raise ValueError(f"{name}: rounds must be at least 1")
+    cur, stats = src, []
+    for _ in range(rounds):
+        n = stats_only(cur, **rule)["out_keys"]
+        dst = KmerCounter(dataclasses.replace(src.cfg, table_slots=n + n // 8 + 4096, bf_enable=False, est_unique=0,
+                                              batch_bytes=1 << 20))
+        try:
+            st = into(dst, cur, **rule)
+            dst.finish()
+        except Exception:
+            dst.close()
+            if cur is not src:
+                cur.close()
+            raise
+        if cur is not src:
+            cur.close()
+        cur = dst
+        stats.append(st)
+        if done(st):
+            break
+    return cur, stats
+
+
 def _clean_desc(min_count, max_count, tip_max_nodes, iso_max_nodes, max_mean) -> kc_clean_desc:
     return kc_clean_desc(int(min_count), int(max_count), int(tip_max_nodes), int(iso_max_nodes), int(max_mean), 0)
 
@@ -1131,28 +1158,8 @@ def clean_rounds(src: KmerCounter, rounds: int, **rule) -> Tuple[KmerCounter, Li
     min_abundance and device; no Bloom filter, a 1 MiB stage: it is read, not counted into) and
     cleans into it; the intermediate table before it is closed (src never is).
     The rounds stop early after one that removes nothing.  The caller closes the result."""
-    if rounds < 1:
-        raise ValueError("clean_rounds: rounds must be at least 1")
-    cur, stats = src, []
-    for _ in range(rounds):
-        n = clean_stats(cur, **rule)["out_keys"]
-        dst = KmerCounter(dataclasses.replace(src.cfg, table_slots=n + n // 8 + 4096, bf_enable=False, est_unique=0,
-                                              batch_bytes=1 << 20))
-        try:
-            st = dst.clean(cur, **rule)
-            dst.finish()
-        except Exception:
-            dst.close()
-            if cur is not src:
-                cur.close()
-            raise
-        if cur is not src:
-            cur.close()
-        cur = dst
-        stats.append(st)
-        if st["tips"] == 0 and st["isolated"] == 0:
-            break
-    return cur, stats
+    return _filter_rounds("clean_rounds", src, rounds, clean_stats, KmerCounter.clean,
+                          lambda st: st["tips"] == 0 and st["isolated"] == 0, rule)
 
 
 def _bubble_desc(min_count, max_count, max_nodes, max_diff, max_mean) -> kc_bubble_desc:
@@ -1176,28 +1183,8 @@ def pop_rounds(src: KmerCounter, rounds: int, **rule) -> Tuple[KmerCounter, List
     slots (src's k, mode, min_abundance and device; no Bloom filter, a 1 MiB stage: it is read, not
     counted into) and pops into it; the intermediate table before it is closed (src never is).
     The rounds stop early after one that pops nothing.  The caller closes the result."""
-    if rounds < 1:
-        raise ValueError("pop_rounds: rounds must be at least 1")
-    cur, stats = src, []
-    for _ in range(rounds):
-        n = bubble_stats(cur, **rule)["out_keys"]
-        dst = KmerCounter(dataclasses.replace(src.cfg, table_slots=n + n // 8 + 4096, bf_enable=False, est_unique=0,
-                                              batch_bytes=1 << 20))
-        try:
-            st = dst.pop_bubbles(cur, **rule)
-            dst.finish()
-        except Exception:
-            dst.close()
-            if cur is not src:
-                cur.close()
-            raise
-        if cur is not src:
-            cur.close()
-        cur = dst
-        stats.append(st)
-        if st["popped"] == 0:
-            break
-    return cur, stats
+    return _filter_rounds("pop_rounds", src, rounds, bubble_stats, KmerCounter.pop_bubbles,
+                          lambda st: st["popped"] == 0, rule)
 
 
 def digest_dict(lines: int, count_sum: int, hash_sum: int, hash_xor: int) -> dict:
