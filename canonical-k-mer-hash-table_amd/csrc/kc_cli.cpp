@@ -38,7 +38,7 @@ namespace {
 
 enum CliExit { kConversion = 104, kValidation = 105, kRequired = 106, kRequires = 107, kExcludes = 108, kExtras = 109 };
 
-// the six options --clean-* and --pop-* both have: --X-max-mean, --X-rounds, --X-min, --X-max,
+// the six options --clean-*, --pop-* and --cut-* all have: --X-max-mean, --X-rounds, --X-min, --X-max,
 // --X-out, --X-stats (take_filter_opt, check_filter_opts)
 struct FilterOpts {
     unsigned long long max_mean = 0, rounds = 1, min = 0, max = 0;
@@ -120,6 +120,14 @@ struct Args {
     unsigned long long pop_nodes = 0, pop_max_diff = 0;
     bool pop_set = false;
     FilterOpts pop;
+    // --cut-weak N [--cut-ratio P] [--cut-max-mean M] [--cut-rounds R] [--cut-min N] [--cut-max N]
+    // [--cut-out FILE] [--cut-stats FILE]: weak-link removal (kc_cut_weak) of the counted table -- of
+    // the one the --clean-* and --pop-* rounds left when those are given too -- into a new one, R
+    // rounds at the most, which --graph, --unitigs and --gfa then read.  The range as for --clean-min /
+    // --clean-max.
+    unsigned long long cut_nodes = 0, cut_ratio = 200;
+    bool cut_set = false;
+    FilterOpts cut;
 };
 
 const char* const kOpNames[] = {"intersect-min", "intersect-sum", "intersect-left", "subtract",
@@ -199,7 +207,20 @@ void usage(const char* prog) {
                  "                              after a round that pops nothing (def. 1)\n"
                  "  --pop-min,--pop-max UINT    a k-mer is a node when its count is in this range (def. the -a value and up)\n"
                  "  --pop-out FILE              write every k-mer of the popped table, as -o writes the counted one's\n"
-                 "  --pop-stats FILE            a line of \"<name> <value>\" pairs per round\n\n"
+                 "  --pop-stats FILE            a line of \"<name> <value>\" pairs per round\n"
+                 "  --cut-weak UINT             cut the graph's weak links (after the --clean-* and --pop-* rounds, on the\n"
+                 "                              table those left): a unitig of at most this many k-mers (k to 2 k is\n"
+                 "                              customary) that is connected at both ends goes when its mean count is\n"
+                 "                              low beside its neighbours'; --graph, --unitigs and --gfa then read the result\n"
+                 "  --cut-ratio UINT            ... below this many thousandths of the mean count of the unitigs around\n"
+                 "                              it (def. 200; at most 1000; from about 500 both arms of a bubble go;\n"
+                 "                              0: no such test, --cut-max-mean alone decides)\n"
+                 "  --cut-max-mean UINT         never cut a unitig whose mean count is above this (def. no guard)\n"
+                 "  --cut-rounds UINT           cutting rounds, each on the result of the one before; they stop early\n"
+                 "                              after a round that cuts nothing (def. 1)\n"
+                 "  --cut-min,--cut-max UINT    a k-mer is a node when its count is in this range (def. the -a value and up)\n"
+                 "  --cut-out FILE              write every k-mer of the cut table, as -o writes the counted one's\n"
+                 "  --cut-stats FILE            a line of \"<name> <value>\" pairs per round\n\n"
                  "Mandatory params:\n"
                  "  -s,--hash-tab-size UINT     Hash table size\n"
                  "  -u,--unq-kmers UINT         Estimated number of unique k-mers\n";
@@ -231,7 +252,7 @@ bool parse_double(const std::string& s, double* v) {
     return end && *end == 0;
 }
 
-// o = v as one of FilterOpts' six under `prefix` ("--clean-", "--pop-"): 1 taken, 0 not one of them,
+// o = v as one of FilterOpts' six under `prefix` ("--clean-", "--pop-", "--cut-"): 1 taken, 0 not one of them,
 // -1 one of them whose value is no 32-bit number
 int take_filter_opt(FilterOpts* f, const std::string& prefix, const std::string& o, const std::string& v) {
     const std::string name = o.compare(0, prefix.size(), prefix) == 0 ? o.substr(prefix.size()) : "";
@@ -246,7 +267,7 @@ int take_filter_opt(FilterOpts* f, const std::string& prefix, const std::string&
     return 1;
 }
 
-// What both families check once all options are read (on: the family's switch was given); the
+// What every family checks once all options are read (on: the family's switch was given); the
 // range's default as for --graph-min.  -1: fine, else the exit code.
 int check_filter_opts(FilterOpts* f, bool on, const std::string& prefix, const Args& a, const char* requires_text,
                       const char* excludes_text) {
@@ -442,15 +463,19 @@ int parse(int argc, char** argv, Args* a) {
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 (o == "--gfa-min" ? a->gfa_min : a->gfa_max) = u;
                 (o == "--gfa-min" ? a->gfa_min_set : a->gfa_max_set) = true;
-            } else if (int t = take_filter_opt(&a->clean, "--clean-", o, v) | take_filter_opt(&a->pop, "--pop-", o, v)) {
-                if (t < 0) return cli_error(kConversion, "Could not convert: " + o + " = " + v);  // (the other call gave 0)
-            } else if (o == "--clean-tips" || o == "--clean-isolated" || o == "--pop-bubbles" || o == "--pop-max-diff") {
+            } else if (int t = take_filter_opt(&a->clean, "--clean-", o, v) | take_filter_opt(&a->pop, "--pop-", o, v) |
+                               take_filter_opt(&a->cut, "--cut-", o, v)) {
+                if (t < 0) return cli_error(kConversion, "Could not convert: " + o + " = " + v);  // (the other calls gave 0)
+            } else if (o == "--clean-tips" || o == "--clean-isolated" || o == "--pop-bubbles" || o == "--pop-max-diff" ||
+                       o == "--cut-weak" || o == "--cut-ratio") {
                 if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
                 (o == "--clean-tips" ? a->clean_tips : o == "--clean-isolated" ? a->clean_iso
-                 : o == "--pop-bubbles" ? a->pop_nodes : a->pop_max_diff) = u;
+                 : o == "--pop-bubbles" ? a->pop_nodes : o == "--pop-max-diff" ? a->pop_max_diff
+                 : o == "--cut-weak" ? a->cut_nodes : a->cut_ratio) = u;
                 (o == "--clean-tips" ? a->clean_tips_set : o == "--clean-isolated" ? a->clean_iso_set
-                 : o == "--pop-bubbles" ? a->pop_set : a->pop.dep_set) = true;
+                 : o == "--pop-bubbles" ? a->pop_set : o == "--pop-max-diff" ? a->pop.dep_set
+                 : o == "--cut-weak" ? a->cut_set : a->cut.dep_set) = true;
             } else if (o == "--op") {
                 a->op_name = v;
                 for (int q = 0; q < 7; q++)
@@ -523,6 +548,12 @@ int parse(int argc, char** argv, Args* a) {
                             "--pop-max-diff/--pop-max-mean/--pop-rounds/--pop-min/--pop-max/--pop-out/--pop-stats "
                             "require --pop-bubbles", "--pop-bubbles excludes --op");
     if (bad >= 0) return bad;
+    bad = check_filter_opts(&a->cut, a->cut_set, "--cut-", *a,
+                            "--cut-ratio/--cut-max-mean/--cut-rounds/--cut-min/--cut-max/--cut-out/--cut-stats "
+                            "require --cut-weak", "--cut-weak excludes --op");
+    if (bad >= 0) return bad;
+    if (a->cut_ratio > 1000)
+        return cli_error(kValidation, "--cut-ratio: Value " + std::to_string(a->cut_ratio) + " not in range 0 to 1000");
     if (!a->op_name.empty() && a->with.empty()) return cli_error(kRequires, "--op requires --with");
     if (a->op_name.empty() && !a->with.empty()) return cli_error(kRequires, "--with requires --op");
     if (a->range_set && a->op_name.empty()) return cli_error(kRequires, "--a-min/--a-max/--b-min/--b-max require --op");
@@ -1378,7 +1409,7 @@ int main(int argc, char** argv) {
         std::cout << "Corrected " << bases << " bases in " << recs << " of " << nrec << " records (" << cands
                   << " candidates, " << ambig << " ambiguous, " << dropped << " dropped)\n";
     }
-    // --clean-tips / --clean-isolated and --pop-bubbles (extensions): up to --X-rounds rounds of a graph
+    // --clean-tips / --clean-isolated, --pop-bubbles and --cut-weak (extensions): up to --X-rounds rounds of a graph
     // filter, each into a new table sized from a statistics-only call -- no Bloom filter, every k-mer
     // of it output (-a 1) -- which the three graph outputs below read instead of the counted table
     kc_ctx* gctx = ctx;
@@ -1487,6 +1518,34 @@ int main(int argc, char** argv) {
                               << bs.popped_nodes << " nodes); kept " << bs.out_keys << " k-mers in " << slots << " slots\n";
                 },
                 [](const kc_bubble_stats& bs) { return !bs.popped; }))
+            return quit();
+    }
+    // (--cut-weak reads the table the popping left, or the cleaning, or the counted one)
+    if (a.cut_set) {
+        kc_weak_desc wd;
+        std::memset(&wd, 0, sizeof wd);
+        wd.min_count = (uint32_t)a.cut.min;
+        wd.max_count = (uint32_t)a.cut.max;
+        wd.max_nodes = (uint32_t)a.cut_nodes;
+        wd.ratio_permille = (uint32_t)a.cut_ratio;
+        wd.max_mean = (uint32_t)a.cut.max_mean;
+        kc_weak_stats ws;
+        if (!filter_rounds(
+                a.cut, "weak-link removal", "writing the cut table's k-mers", &ws,
+                [&](kc_ctx* dst, kc_ctx* src, kc_weak_stats* st) { return kc_cut_weak(dst, src, &wd, st); },
+                [](FILE* sf, unsigned long long round, const kc_weak_stats& ws) {
+                    std::fprintf(sf, "round %llu unitigs %llu nodes %llu interior %llu weak %llu cut %llu cut_nodes %llu "
+                                     "out_keys %llu out_sum %llu\n", round, (unsigned long long)ws.unitigs,
+                                 (unsigned long long)ws.nodes, (unsigned long long)ws.interior, (unsigned long long)ws.weak,
+                                 (unsigned long long)ws.cut, (unsigned long long)ws.cut_nodes,
+                                 (unsigned long long)ws.out_keys, (unsigned long long)ws.out_sum);
+                },
+                [](unsigned long long round, const kc_weak_stats& ws, auto slots) {
+                    std::cout << "Weak-link removal round " << round << ": " << ws.unitigs << " unitigs, " << ws.nodes << " nodes, "
+                              << ws.interior << " interior, " << ws.weak << " of them weak; cut " << ws.cut << " ("
+                              << ws.cut_nodes << " nodes); kept " << ws.out_keys << " k-mers in " << slots << " slots\n";
+                },
+                [](const kc_weak_stats& ws) { return !ws.cut; }))
             return quit();
     }
     if (!a.graph.empty() || !a.graph_stats.empty()) {  // extension: the de Bruijn graph of the counted (or cleaned, popped) k-mers
@@ -1607,7 +1666,7 @@ int main(int argc, char** argv) {
     std::cout << "Time used to write k-mers in a file: "
               << std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() << " microseconds\n";
     if (!a.histo.empty() || !a.query.empty() || !a.coverage.empty() || !a.correct.empty() || !a.graph.empty() ||
-        !a.graph_stats.empty() || !a.unitigs.empty() || !a.gfa.empty() || a.cleaning() || a.pop_set)
+        !a.graph_stats.empty() || !a.unitigs.empty() || !a.gfa.empty() || a.cleaning() || a.pop_set || a.cut_set)
         std::cout << "Time used to query the hash table: "
                   << std::chrono::duration_cast<std::chrono::microseconds>(t3 - t2).count() << " microseconds"
                   << (a.query.empty() ? "" : " (" + std::to_string(qlines.size()) + " queries)")

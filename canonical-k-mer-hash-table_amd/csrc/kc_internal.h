@@ -613,9 +613,23 @@ struct BubbleOps {
                           unsigned long long* stats, hipStream_t s);
 };
 
+// Weak-link removal (include/kc_api.h kc_cut_weak_device; kc_weak_impl.h), between the same two
+// launches as bubble popping, on a ranking with verdict bytes and nothing more.  cut zeroes the
+// verdict bytes and writes CLEAN_WEAK at the start id of every cut unitig; stats (nullptr: none)
+// receives the first six words of kc_weak_stats, added to.
+constexpr uint8_t CLEAN_WEAK = 4;
+struct WeakRule {
+    uint32_t max_nodes, ratio_permille, max_mean;  // kc_weak_desc's
+};
+template <int W>
+struct WeakOps {
+    static hipError_t cut(TableView src, int k, UnitigBufs u, int rounds, WeakRule rule, unsigned long long* stats,
+                          hipStream_t s);
+};
+
 // Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip, kc_unitig.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
-// JoinOps, GraphOps, UnitigOps, CleanOps, BubbleOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_clean_w.hip, kc_bubble_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// JoinOps, GraphOps, UnitigOps, CleanOps, BubbleOps, WeakOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_clean_w.hip, kc_bubble_w.hip, kc_weak_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

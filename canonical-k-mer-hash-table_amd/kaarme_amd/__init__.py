@@ -68,7 +68,7 @@ EXPORTS = (
     "kc_unitigs_device", "kc_unitigs",
     "kc_unitig_graph_device", "kc_unitig_graph",
     "kc_clean_device", "kc_clean",
-    "kc_pop_bubbles_device", "kc_pop_bubbles",
+    "kc_pop_bubbles_device", "kc_pop_bubbles", "kc_cut_weak_device", "kc_cut_weak",
 )
 # kc_graph* node flags (KC_GRAPH_*): bits 0-7 the edges -- bit y: canon(c[1:] + y) is a node (side
 # R), bit 4 + y: canon(y + c[:-1]) is a node (side L) -- then the two unitig links and the node bit
@@ -231,6 +231,22 @@ class kc_bubble_stats(ctypes.Structure):  # 64 bytes
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class kc_weak_desc(ctypes.Structure):  # 24 bytes
+    _fields_ = [(n, ctypes.c_uint32) for n in ("min_count", "max_count", "max_nodes", "ratio_permille", "max_mean",
+                                               "reserved")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class kc_weak_stats(ctypes.Structure):  # 64 bytes
+    _fields_ = [(n, ctypes.c_uint64) for n in ("unitigs", "nodes", "interior", "weak", "cut", "cut_nodes", "out_keys",
+                                               "out_sum")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class kc_correct_stat(ctypes.Structure):  # 16 bytes
     _fields_ = [(n, ctypes.c_uint32) for n in ("candidates", "corrected", "ambiguous", "dropped")]
 
@@ -352,6 +368,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_clean": (I32, [P, P, ctypes.POINTER(kc_clean_desc), ctypes.POINTER(kc_clean_stats)]),
         "kc_pop_bubbles_device": (I32, [P, P, ctypes.POINTER(kc_bubble_desc), P, P]),
         "kc_pop_bubbles": (I32, [P, P, ctypes.POINTER(kc_bubble_desc), ctypes.POINTER(kc_bubble_stats)]),
+        "kc_cut_weak_device": (I32, [P, P, ctypes.POINTER(kc_weak_desc), P, P]),
+        "kc_cut_weak": (I32, [P, P, ctypes.POINTER(kc_weak_desc), ctypes.POINTER(kc_weak_stats)]),
         "kc_unitig_graph_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, U64, P, P]),
         "kc_unitig_graph": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
                                   ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
@@ -1068,6 +1086,31 @@ class KmerCounter:
         self._chk(self.lib.kc_pop_bubbles(self._ctx, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_pop_bubbles")
         return st.as_dict()
 
+    # -- weak-link removal (kc_cut_weak*): this counter is the destination
+    def cut_weak_device(self, src: "KmerCounter", min_count: int = 1, max_count: int = 0, max_nodes: int = 0,
+                        ratio_permille: int = 0, max_mean: int = 0, stats_ptr: int = 0, stream: int = 0):
+        """self += the graph of src's k-mers with min_count <= T(c) <= max_count without its short
+        interior unitigs of low local coverage: an open, non-palindromic unitig whose ends both have
+        an edge, of at most max_nodes nodes (0: nothing is cut; k to 2 k is customary), is dropped
+        when its mean T(c) is below ratio_permille / 1000 of the mean T(c) over the nodes of the
+        unitigs its edges lead to (0: no relative test; 100 to 200 is customary, and from about 500
+        both arms of an even bubble go); none is dropped whose mean T(c) is above max_mean (0: no
+        guard); raw counts, all in HBM.  stats_ptr: 64 bytes of device memory for the kc_weak_stats
+        (0: none); enqueued on `stream`, no wait."""
+        d = _weak_desc(min_count, max_count, max_nodes, ratio_permille, max_mean)
+        self._chk(self.lib.kc_cut_weak_device(self._ctx, src._ctx, ctypes.byref(d), ctypes.c_void_p(stats_ptr or None),
+                                              ctypes.c_void_p(stream or None)), "kc_cut_weak_device")
+
+    def cut_weak(self, src: "KmerCounter", min_count: int = 1, max_count: int = 0, max_nodes: int = 0,
+                 ratio_permille: int = 0, max_mean: int = 0) -> dict:
+        """cut_weak_device that waits; returns the statistics: unitigs and nodes of the range's graph,
+        interior, weak (interior unitigs that are weak, whatever max_nodes and the guard say), cut and
+        cut_nodes (what was dropped), out_keys and out_sum (the kept nodes and their raw counts,
+        added here)."""
+        d, st = _weak_desc(min_count, max_count, max_nodes, ratio_permille, max_mean), kc_weak_stats()
+        self._chk(self.lib.kc_cut_weak(self._ctx, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_cut_weak")
+        return st.as_dict()
+
     def compact_read(self, info: dict):
         """(slot words, secondary-array words) as uint64 arrays."""
         W = self.lib.kc_key_words(self._ctx)
@@ -1111,7 +1154,7 @@ def table_compare(a: KmerCounter, b: KmerCounter, a_range=(1, 0), b_range=(1, 0)
 
 
 def _filter_rounds(name, src, rounds, stats_only, into, done, rule) -> Tuple[KmerCounter, List[dict]]:
-    """The round driver of clean_rounds and pop_rounds: stats_only(cur, **rule) sizes the next table,
+    """The round driver of clean_rounds, pop_rounds and weak_rounds: stats_only(cur, **rule) sizes the next table,
     into(dst, cur, **rule) fills it, done(statistics) ends the rounds early."""
     if rounds < 1:
         raise ValueError(f"{name}: rounds must be at least 1")
@@ -1185,6 +1228,30 @@ def pop_rounds(src: KmerCounter, rounds: int, **rule) -> Tuple[KmerCounter, List
     The rounds stop early after one that pops nothing.  The caller closes the result."""
     return _filter_rounds("pop_rounds", src, rounds, bubble_stats, KmerCounter.pop_bubbles,
                           lambda st: st["popped"] == 0, rule)
+
+
+def _weak_desc(min_count, max_count, max_nodes, ratio_permille, max_mean) -> kc_weak_desc:
+    return kc_weak_desc(int(min_count), int(max_count), int(max_nodes), int(ratio_permille), int(max_mean), 0)
+
+
+def weak_stats(src: KmerCounter, min_count: int = 1, max_count: int = 0, max_nodes: int = 0, ratio_permille: int = 0,
+               max_mean: int = 0) -> dict:
+    """The statistics of KmerCounter.cut_weak without a destination (kc_cut_weak with dst NULL):
+    nothing is inserted anywhere, and out_keys sizes a destination."""
+    d, st = _weak_desc(min_count, max_count, max_nodes, ratio_permille, max_mean), kc_weak_stats()
+    src._chk(src.lib.kc_cut_weak(None, src._ctx, ctypes.byref(d), ctypes.byref(st)), "kc_cut_weak")
+    return st.as_dict()
+
+
+def weak_rounds(src: KmerCounter, rounds: int, **rule) -> Tuple[KmerCounter, List[dict]]:
+    """Up to `rounds` rounds of weak-link removal, each on the result of the one before (cutting joins
+    unitigs, which changes the neighbours of what is left): (the last round's table, the statistics
+    of every round run).  rule: cut_weak()'s keywords, the same in every round.  A round first asks
+    for the statistics alone, creates a table of out_keys + out_keys / 8 + 4096 slots (src's k, mode,
+    min_abundance and device; no Bloom filter, a 1 MiB stage: it is read, not counted into) and cuts
+    into it; the intermediate table before it is closed (src never is).
+    The rounds stop early after one that cuts nothing.  The caller closes the result."""
+    return _filter_rounds("weak_rounds", src, rounds, weak_stats, KmerCounter.cut_weak, lambda st: st["cut"] == 0, rule)
 
 
 def digest_dict(lines: int, count_sum: int, hash_sum: int, hash_xor: int) -> dict:

@@ -853,6 +853,82 @@ typedef struct {            /* 64 bytes */
 int kc_pop_bubbles_device(kc_ctx* dst, kc_ctx* src, const kc_bubble_desc* d, kc_bubble_stats* dev_stats, void* hip_stream);
 int kc_pop_bubbles(kc_ctx* dst, kc_ctx* src, const kc_bubble_desc* d, kc_bubble_stats* stats);
 
+/* Weak-link removal: the graph of src's range without its short interior unitigs of low local
+ * coverage, as a new counted table -- the third simplification that MEGAHIT (remove low local
+ * coverage), SPAdes (low-coverage edge remover, erroneous-connection remover) and Velvet (coverage
+ * cutoff) run beside tip clipping and bubble popping.  A chimeric read, or a stray path of error
+ * k-mers that lands between two real paths, leaves a short unitig of count about 1 that is connected
+ * at both ends: neither a tip nor isolated, and no bubble arm unless a parallel arm happens to exist.
+ * All terms are kc_graph_device's, kc_unitig_graph_device's and kc_clean_device's: node, range
+ * [min_count, max_count], side, edge bits, unitig, unitig end, degree of an end, palindromic unitig,
+ * circular, edge (from, from_rev, to, to_rev), count_sum, n.
+ *   interior      U is open and not palindromic, and both its ends have degree >= 1.  Degree is
+ *                 kc_clean's: the popcount of the end's edge nibble, self edges included.
+ *   neighbours    the multiset N(U) with one entry V for every edge of kc_unitig_graph's list that has
+ *                 from = U and to = V != U.  N(U) has at most eight entries.  A V reached by two
+ *                 edges counts twice, whether it hangs on both ends of U or twice on one end.  Edges
+ *                 that lead back into U -- a hairpin, a homopolymer's loop -- give no entry.
+ *                 Neighbours are always open unitigs; they may be palindromic.
+ *   local         local_sum = the sum of count_sum(V) and local_n = the sum of n(V) over N(U).
+ *   weak          U is weak when N(U) is not empty and either ratio_permille == 0 or
+ *                   count_sum(U) * local_n * 1000 < ratio_permille * local_sum * n(U),
+ *                 compared strictly and exactly (T(c) is a 32-bit value and ids are below 2^30, so
+ *                 each side is below 2^106: the products need 128 bits).  In words: the mean T(c) of
+ *                 U is below ratio_permille / 1000 of the mean T(c) over its neighbours' nodes.
+ *   cut           U is cut when max_nodes != 0 and n(U) <= max_nodes, the guard passes (max_mean == 0
+ *                 or count_sum(U) <= (uint64_t)max_mean * n(U)), and U is interior and weak.
+ *   order         every verdict is taken on the one graph, so removals are simultaneous and depend
+ *                 on no order.  Cutting joins unitigs, so rounds compose by calling it again on dst,
+ *                 and with kc_clean and kc_pop_bubbles by calling one on another's dst.
+ *   hazard        the rule knows no parallel arm.  A ratio_permille at or above roughly 500 cuts BOTH
+ *                 arms of an even heterozygous bubble: each arm has about half the mean of the two
+ *                 unitigs around it.  The customary values are max_nodes = k to 2 k and
+ *                 ratio_permille = 100 to 200.
+ *   kept nodes    every node of a unitig that is not cut.  Each kept node's raw count (the slot's
+ *                 count, not T(c)) is added into dst exactly as kc_table_op_device adds its results:
+ *                 a fresh dst holds exactly the cut graph, repeated calls accumulate,
+ *                 kc_stats.inserted grows by the counts added, a dst that is too small makes
+ *                 kc_finish(dst) return KC_ERR_TABLE_FULL, and a compact snapshot of dst is dropped.
+ *                 K-mers of src outside the range are not nodes and are not copied; with max_nodes
+ *                 == 0 the call copies the range's nodes.
+ *   statistics    dst == NULL fills only the statistics: that call sizes a destination.  nodes ==
+ *                 out_keys + cut_nodes always.
+ *   kc_cut_weak_device  follows the *_device rule for both contexts as kc_table_op_device does and
+ *                 has no host wait; its node ids are sized by src's table slots, as
+ *                 kc_unitig_graph_device's.  dev_stats (device memory) may be NULL.
+ *   kc_cut_weak   counts the ids first (the k-mers with T(c) >= min_count), runs the ranking once
+ *                 and waits for the answer; stats (host memory) may be NULL.
+ * Errors: KC_ERR_ARG for dst == src, a different k or device, reserved != 0, min_count above a
+ * non-zero max_count, k < 2, a NULL src or desc, ratio_permille > 1000, and max_nodes != 0 with
+ * ratio_permille == 0 and max_mean == 0 (that would cut every short interior unitig); KC_ERR_STATE
+ * when either context has no table or a failed pass left it incomplete; KC_ERR_NOMEM when the scratch
+ * does not fit, reported before any kernel of the call (kc_cut_weak: of the ranking) is launched.  The
+ * message goes on dst, or on src when dst is NULL.  An emptied src gives all-zero statistics and adds
+ * nothing.  src's table and kc_stats never change.
+ * Method: kc_unitigs_device's ranking and its records' kernel as they are, then one pass over the
+ * node ids in which the node at position 0 of every open unitig whose ends both have an edge walks
+ * the set bits of its two end nibbles, probes each neighbour once, follows slot -> id -> first node,
+ * adds that unitig's n and count_sum and writes the verdict at its id; and kc_clean_device's copy of
+ * the kept nodes.  An interior unitig costs at most eight probes.  Nothing is added to kc_clean*'s
+ * scratch of src:
+ *   scratch = 5 * table_slots + 141 * ids bytes,  ids as for kc_unitigs* (< 2^30, else KC_ERR_NOMEM). */
+typedef struct {            /* 24 bytes */
+    uint32_t min_count, max_count;   /* the range, as kc_graph_device's */
+    uint32_t max_nodes;        /* 0: nothing is cut, the call copies the range's nodes */
+    uint32_t ratio_permille;   /* 0: no relative test; at most 1000 */
+    uint32_t max_mean;         /* 0: no guard */
+    uint32_t reserved;         /* 0 */
+} kc_weak_desc;
+typedef struct {            /* 64 bytes */
+    uint64_t unitigs, nodes;   /* of the range's graph: kc_unitig_stats' */
+    uint64_t interior;         /* interior unitigs */
+    uint64_t weak;             /* interior unitigs that are weak, whatever max_nodes and the guard say */
+    uint64_t cut, cut_nodes;   /* cut unitigs and their nodes */
+    uint64_t out_keys, out_sum;   /* kept nodes and the sum of their raw counts (added to dst when dst != NULL) */
+} kc_weak_stats;
+int kc_cut_weak_device(kc_ctx* dst, kc_ctx* src, const kc_weak_desc* d, kc_weak_stats* dev_stats, void* hip_stream);
+int kc_cut_weak(kc_ctx* dst, kc_ctx* src, const kc_weak_desc* d, kc_weak_stats* stats);
+
 /* Re-initialise the table, the Bloom filter and all counters (the table/filter
  * constructors again, without reallocating). */
 int kc_reset(kc_ctx* ctx);
