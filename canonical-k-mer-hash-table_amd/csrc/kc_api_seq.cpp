@@ -13,7 +13,7 @@ static int seq_ready(kc_ctx* c) {
 }
 
 // the packed stream of a pass of up to n bytes (3/8 byte per byte)
-static int seq_stream_bufs(kc_ctx* c, uint64_t n) {
+int seq_stream_bufs(kc_ctx* c, uint64_t n) {
     const uint64_t nw = seq_pack_words(n);
     if (c->d_seq_pk.capacity() < nw || c->d_seq_bk.capacity() < nw) make_room(c, nw * 12);
     if (!reserve_pair(c->d_seq_pk, nw, c->d_seq_bk, nw))

@@ -108,9 +108,10 @@ static int unitig_to_host(kc_ctx* c, std::unique_ptr<T, StdFree>* out, const T* 
 
 // The device form of kc_unitigs* and, with_edges, of kc_unitig_graph*, which adds the record index
 // per id to the scratch, the edges' launch and the three statistics words behind kc_unitig_stats.
-static int unitigs_device(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs,
-                          uint64_t cap_unitigs, uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
-                          void* stats, hipStream_t s) {
+// after (kc_read_paths_device, kc_api_path.cpp): its scratch before the ranking's, its kernels behind the call's.
+int unitigs_device(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs,
+                   uint64_t cap_unitigs, uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
+                   void* stats, hipStream_t s, UnitigAfter* after) {
     if (!c) return KC_ERR_ARG;
     int rc = unitig_check(c, min_count, max_count);
     if (rc) return rc;
@@ -120,6 +121,7 @@ static int unitigs_device(kc_ctx* c, bool with_edges, uint32_t min_count, uint32
     StreamScope on(c, s);
     if ((rc = on.join())) return rc;
     if ((rc = materialize_zero(c, s))) return rc;  // an emptied table has no unitigs
+    if (after && (rc = after->prepare(c))) return rc;
     UnitigRanked r;
     // no host wait, so the ids are sized by what the host knows: the table's slots
     if ((rc = unitig_rank(c, min_count, max_count, c->nbuckets * (uint64_t)c->S, with_edges ? UNITIG_GRAPH : UNITIG_PLAIN, s, &r)))
@@ -131,13 +133,15 @@ static int unitigs_device(kc_ctx* c, bool with_edges, uint32_t min_count, uint32
     if (stats)
         HIPCHK(c, hipMemcpyAsync(stats, r.u.ctl + UC_STATS, with_edges ? sizeof(kc_cdbg_stats) : sizeof(kc_unitig_stats),
                                  hipMemcpyDeviceToDevice, s));
+    if (after && (rc = after->run(c, r, rec, s))) return rc;
     return on.finish();
 }
 
 // The host form of kc_unitigs* and, with_edges, of kc_unitig_graph*: rank once, read the totals
 // (records and edges counted without buffers), allocate, write.
-static int unitigs_host(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
-                        kc_unitig_edge** edges, void* stats) {
+// after (kc_read_paths): behind the last records' launch, whose numbering rec holds; it waits itself.
+int unitigs_host(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+                 kc_unitig_edge** edges, void* stats, UnitigAfter* after) {
     if (!c) return KC_ERR_ARG;
     if (unitigs) *unitigs = nullptr;
     if (bases) *bases = nullptr;
@@ -171,6 +175,7 @@ static int unitigs_host(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t
             return rc;
         if (want_e) HIPCHK(c, launch_unitig_edges(table_view(c), c->cfg.k, r.u, rec, de.get(), h.edges, s));
     }
+    if (after && (rc = after->run(c, r, rec, s))) return rc;
     std::unique_ptr<kc_unitig, StdFree> out_r;
     std::unique_ptr<uint8_t, StdFree> out_b;
     std::unique_ptr<kc_unitig_edge, StdFree> out_e;
@@ -193,12 +198,12 @@ extern "C" {
 int kc_unitigs_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs, uint64_t cap_unitigs,
                       uint8_t* bases, uint64_t cap_bases, kc_unitig_stats* stats, void* sp) {
     return unitigs_device(c, false, min_count, max_count, unitigs, cap_unitigs, bases, cap_bases, nullptr, 0, stats,
-                          (hipStream_t)sp);
+                          (hipStream_t)sp, nullptr);
 }
 
 int kc_unitigs(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
                kc_unitig_stats* stats) {
-    return unitigs_host(c, false, min_count, max_count, unitigs, bases, nullptr, stats);
+    return unitigs_host(c, false, min_count, max_count, unitigs, bases, nullptr, stats, nullptr);
 }
 
 // ---- the compacted graph: the unitigs and the edges between them (kc_unitig_graph*) -----------------
@@ -206,12 +211,12 @@ int kc_unitig_graph_device(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc
                            uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
                            kc_cdbg_stats* stats, void* sp) {
     return unitigs_device(c, true, min_count, max_count, unitigs, cap_unitigs, bases, cap_bases, edges, cap_edges, stats,
-                          (hipStream_t)sp);
+                          (hipStream_t)sp, nullptr);
 }
 
 int kc_unitig_graph(kc_ctx* c, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
                     kc_unitig_edge** edges, kc_cdbg_stats* stats) {
-    return unitigs_host(c, true, min_count, max_count, unitigs, bases, edges, stats);
+    return unitigs_host(c, true, min_count, max_count, unitigs, bases, edges, stats, nullptr);
 }
 
 }  // extern "C"

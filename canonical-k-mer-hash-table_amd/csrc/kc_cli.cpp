@@ -33,6 +33,7 @@
 
 #include "../../include/kc_api.h"
 #include "kc_unitig_host.h"
+#include "kc_path_host.h"
 
 namespace {
 
@@ -102,6 +103,10 @@ struct Args {
     // --gfa FILE [--gfa-min N] [--gfa-max N]: the compacted graph (kc_unitig_graph) as GFA 1.0, the
     // unitigs as segments and the edges between them as links; the range as for --graph
     std::string gfa;
+    // --paths FILE --paths-out FILE [--paths-stats FILE]: the records of FILE (read as --coverage's)
+    // threaded through that compacted graph (kc_read_paths, the one call that then also feeds --gfa's
+    // writer), as GAF: one line per chain, the segment names those of the GFA beside it
+    std::string paths, paths_out, paths_stats;
     unsigned long long gfa_min = 0, gfa_max = 0;
     bool gfa_min_set = false, gfa_max_set = false;
     // --clean-tips N / --clean-isolated N [--clean-max-mean M] [--clean-rounds R] [--clean-min N]
@@ -186,6 +191,12 @@ void usage(const char* prog) {
                  "                              \"L i + i +\", \"L i - i -\" that close a circular unitig\n"
                  "  --gfa-min,--gfa-max UINT    a k-mer is a node when its count is in this range (def. the -a value and\n"
                  "                              up); needs --gfa\n"
+                 "  --paths FILE                sequences (FASTA, FASTQ or one per line) to thread through that graph;\n"
+                 "                              needs --gfa (the segment names are that file's) and --paths-out\n"
+                 "  --paths-out FILE            GAF, a line per chain of consecutive located k-mers: name qlen qstart\n"
+                 "                              qend + path plen pstart pend matches alnlen 255 cg:Z:<alnlen>=\n"
+                 "  --paths-stats FILE          the totals, one per line: seqs windows located runs chains threaded;\n"
+                 "                              needs --paths\n"
                  "  --clean-tips UINT           clean the graph first: remove the dead-end branches (tips) of at most this\n"
                  "                              many k-mers (k - 1 is customary; 0 keeps them); --graph, --unitigs and\n"
                  "                              --gfa then read the cleaned table, every other output the counted one\n"
@@ -458,6 +469,12 @@ int parse(int argc, char** argv, Args* a) {
                 (o == "--unitigs-min" ? a->unitigs_min_set : a->unitigs_max_set) = true;
             } else if (o == "--gfa") {
                 a->gfa = v;
+            } else if (o == "--paths") {
+                a->paths = v;
+            } else if (o == "--paths-out") {
+                a->paths_out = v;
+            } else if (o == "--paths-stats") {
+                a->paths_stats = v;
             } else if (o == "--gfa-min" || o == "--gfa-max") {
                 if (!parse_uint(v, &u) || u > 0xFFFFFFFFull)
                     return cli_error(kConversion, "Could not convert: " + o + " = " + v);
@@ -538,6 +555,10 @@ int parse(int argc, char** argv, Args* a) {
         return cli_error(kValidation, "--unitigs-min: a minimum above its maximum");
     if ((a->gfa_min_set || a->gfa_max_set) && a->gfa.empty())
         return cli_error(kRequires, "--gfa-min/--gfa-max require --gfa");
+    if (!a->paths.empty() && a->gfa.empty()) return cli_error(kRequires, "--paths requires --gfa");
+    if (!a->paths.empty() && a->paths_out.empty()) return cli_error(kRequires, "--paths requires --paths-out");
+    if (a->paths.empty() && !a->paths_out.empty()) return cli_error(kRequires, "--paths-out requires --paths");
+    if (a->paths.empty() && !a->paths_stats.empty()) return cli_error(kRequires, "--paths-stats requires --paths");
     if (!a->gfa_min_set) a->gfa_min = std::min<unsigned long long>(a->min_abundance, 0xFFFFFFFFull);
     if (a->gfa_max && a->gfa_min > a->gfa_max) return cli_error(kValidation, "--gfa-min: a minimum above its maximum");
     int bad = check_filter_opts(&a->clean, a->cleaning(), "--clean-", *a,
@@ -964,6 +985,11 @@ int main(int argc, char** argv) {
     Coverage fix;  // --correct: the same
     if (!a.correct.empty()) {
         const int crc = read_coverage(a.correct, &fix, "--correct");
+        if (crc >= 0) return crc;
+    }
+    Coverage thr;  // --paths: likewise
+    if (!a.paths.empty()) {
+        const int crc = read_coverage(a.paths, &thr, "--paths");
         if (crc >= 0) return crc;
     }
 
@@ -1622,11 +1648,19 @@ int main(int argc, char** argv) {
         uint8_t* ubases = nullptr;
         kc_unitig_edge* uedges = nullptr;
         kc_cdbg_stats cst;
-        if (kc_unitig_graph(gctx, (uint32_t)a.gfa_min, (uint32_t)a.gfa_max, &urec, &ubases, &uedges, &cst) != KC_OK) gdie("gfa");
+        kc_path_run* pruns = nullptr;
+        kc_path_stats pst{};
+        if (a.paths.empty()) {
+            if (kc_unitig_graph(gctx, (uint32_t)a.gfa_min, (uint32_t)a.gfa_max, &urec, &ubases, &uedges, &cst) != KC_OK) gdie("gfa");
+        } else if (kc_read_paths(gctx, (uint32_t)a.gfa_min, (uint32_t)a.gfa_max, &urec, &ubases, &uedges, &cst,
+                                 (const uint8_t*)thr.text.data(), thr.text.size(), thr.offsets.data(), thr.names.size(),
+                                 &pruns, nullptr, &pst) != KC_OK) {
+            gdie("paths");
+        }
         FILE* f = std::fopen(a.gfa.c_str(), "w");
         if (!f) {
             std::cerr << "cannot write " << a.gfa << std::endl;
-            kc_free(urec); kc_free(ubases); kc_free(uedges); kc_destroy(ctx);
+            kc_free(urec); kc_free(ubases); kc_free(uedges); kc_free(pruns); kc_destroy(ctx);
             return 1;
         }
         const unsigned long long ov = (unsigned long long)a.k - 1;
@@ -1647,10 +1681,59 @@ int main(int argc, char** argv) {
             if (urec[i].flags & KC_UNITIG_CIRCULAR)
                 std::fprintf(f, "L\t%llu\t+\t%llu\t+\t%lluM\nL\t%llu\t-\t%llu\t-\t%lluM\n", (unsigned long long)i,
                              (unsigned long long)i, ov, (unsigned long long)i, (unsigned long long)i, ov);
+        bool paths_ok = true;
+        if (!a.paths.empty()) {  // the runs as GAF, a line per chain in run order
+            FILE* g = std::fopen(a.paths_out.c_str(), "w");
+            paths_ok = g != nullptr;
+            kc::GafPath gp;
+            uint64_t chain_seq = 0, qstart = 0;
+            auto flush = [&] {
+                if (!gp.visits) return;
+                const unsigned long long aln = gp.pend - gp.pstart;
+                std::fprintf(g, "%s\t%llu\t%llu\t%llu\t+\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t255\tcg:Z:%llu=\n",
+                             thr.names[chain_seq].c_str(), (unsigned long long)thr.lengths[chain_seq],
+                             (unsigned long long)qstart, (unsigned long long)qstart + aln, gp.path.c_str(),
+                             (unsigned long long)gp.plen, (unsigned long long)gp.pstart, (unsigned long long)gp.pend, aln, aln, aln);
+                gp = kc::GafPath{};
+            };
+            for (uint64_t j = 0; g && j < pst.runs; j++) {
+                const kc_path_run& r = pruns[j];
+                if (!(r.flags & KC_RUN_JOINED)) {
+                    flush();
+                    chain_seq = r.seq;
+                    qstart = r.text_pos - thr.offsets[r.seq];
+                }
+                const kc_unitig& u = urec[r.unitig];
+                kc::gaf_add_run(gp, r.unitig, r.flags & KC_RUN_REV, r.pos, r.windows, u.n_nodes, u.flags & KC_UNITIG_CIRCULAR,
+                                (int)a.k);
+            }
+            if (g) {
+                flush();
+                if (std::fclose(g) != 0) paths_ok = false;
+            }
+            if (!paths_ok) std::cerr << "cannot write " << a.paths_out << std::endl;
+            if (paths_ok && !a.paths_stats.empty()) {
+                FILE* h = std::fopen(a.paths_stats.c_str(), "w");
+                if (h)
+                    std::fprintf(h, "seqs %llu\nwindows %llu\nlocated %llu\nruns %llu\nchains %llu\nthreaded %llu\n",
+                                 (unsigned long long)pst.seqs, (unsigned long long)pst.windows, (unsigned long long)pst.located,
+                                 (unsigned long long)pst.runs, (unsigned long long)pst.chains, (unsigned long long)pst.threaded);
+                if (!h || std::fclose(h) != 0) {
+                    std::cerr << "cannot write " << a.paths_stats << std::endl;
+                    paths_ok = false;
+                }
+            }
+        }
         kc_free(urec);
         kc_free(ubases);
         kc_free(uedges);
+        kc_free(pruns);
         if (std::fclose(f) != 0) { std::cerr << "cannot write " << a.gfa << std::endl; kc_destroy(ctx); return 1; }
+        if (!paths_ok) { kc_destroy(ctx); return 1; }
+        if (!a.paths.empty())
+            std::cout << "Read paths: " << pst.seqs << " sequences, " << pst.windows << " k-mers, " << pst.located
+                      << " located, " << pst.runs << " runs, " << pst.chains << " chains, " << pst.threaded
+                      << " threaded whole\n";
         std::cout << "Compacted graph: " << cst.unitigs << " unitigs (" << cst.circular << " circular), " << cst.nodes
                   << " nodes, " << cst.bases << " bases, longest " << cst.max_nodes << " nodes, " << cst.edges
                   << " edges, " << cst.dead_ends << " dead ends\n";

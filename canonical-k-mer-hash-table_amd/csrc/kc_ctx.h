@@ -255,6 +255,13 @@ struct kc_ctx {
     DevBuf<uint64_t> d_unitig_node;
     DevBuf<unsigned long long> d_unitig_ctl;
     DevBuf<uint32_t> d_unitig_rec;
+    // read paths (kc_api_path.cpp): a place per position of a pass, the tiles' run heads, the control
+    // words (kc_path_stats), and the per-sequence records of a call without dev_seq; beside the
+    // sequence queries' stream and offsets
+    DevBuf<uint2> d_path_place;
+    DevBuf<PathTile> d_path_tiles;
+    DevBuf<unsigned long long> d_path_ctl;
+    DevBuf<kc_path_seq> d_path_seq;
 
     uint64_t n_chunks = 0, n_bytes = 0;
 
@@ -463,6 +470,23 @@ int unitig_check(kc_ctx* c, uint32_t min_count, uint32_t max_count);
 int unitig_bound(kc_ctx* c, uint32_t min_count, unsigned long long* bound);
 int unitig_rank(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t bound, UnitigWants w, hipStream_t s,
                 UnitigRanked* r);
+// What kc_read_paths* (kc_api_path.cpp) adds to the compacted graph's call: prepare reserves its
+// scratch before the ranking's first kernel (the device form), run enqueues its work behind the
+// call's last records launch, whose numbering rec holds.
+struct UnitigAfter {
+    virtual int prepare(kc_ctx* c) = 0;
+    virtual int run(kc_ctx* c, const UnitigRanked& r, const uint32_t* rec, hipStream_t s) = 0;
+
+  protected:
+    ~UnitigAfter() = default;
+};
+int unitigs_device(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig* unitigs,
+                   uint64_t cap_unitigs, uint8_t* bases, uint64_t cap_bases, kc_unitig_edge* edges, uint64_t cap_edges,
+                   void* stats, hipStream_t s, UnitigAfter* after);
+int unitigs_host(kc_ctx* c, bool with_edges, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+                 kc_unitig_edge** edges, void* stats, UnitigAfter* after);
+// kc_api_seq.cpp: the packed stream of a pass of up to n bytes
+int seq_stream_bufs(kc_ctx* c, uint64_t n);
 // kc_api_pass.cpp
 int flush_host(kc_ctx* c);
 int device_pass(kc_ctx* c, const uint8_t* img, const kc_chunk* chunks, size_t n, int fmt, int pass, hipStream_t s);

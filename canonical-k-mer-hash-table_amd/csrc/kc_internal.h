@@ -627,9 +627,48 @@ struct WeakOps {
                           hipStream_t s);
 };
 
-// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip, kc_unitig.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
-// JoinOps, GraphOps, UnitigOps, CleanOps, BubbleOps, WeakOps or CorrectOps, whose members are defined and explicitly instantiated by the translation unit of their width
-// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_clean_w.hip, kc_bubble_w.hip, kc_weak_w.hip, kc_correct_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
+// Read paths (kc_path_impl.h, kc_path.hip; the definitions: include/kc_api.h kc_read_paths_device),
+// after launch_unitig_heads of the same UnitigBufs with rec.  One pass of n_pos text bytes from byte
+// `base` on, holding the sequences i0 .. i1 - 1 of the device offsets off, after launch_seq_pack of
+// the same pass.  locate writes place[p] for every position: {start id, q | rev << 31}, PATH_NONE
+// for a window that is no node, PATH_NOWIN where no window starts in the pass (the end of its
+// sequence is the later kernels' to apply).  runs: the run heads of the pass in position order behind
+// the run cursor ctl[PC_RUNS] (tiles: path_tiles(n_pos) entries of scratch), the records with an
+// index below cap_runs, the sums of every sequence into seq[i] (zeroed by the caller) and first_run,
+// the totals into ctl.  finish adds PC_SEQS and PC_THREADED from the finished seq[i0 .. i1).
+constexpr uint32_t PATH_NONE = 0xFFFFFFFFu, PATH_NOWIN = 0xFEFEFEFEu;
+constexpr int PATH_T = 256;  // positions per tile
+struct PathTile {
+    unsigned long long heads;       // run heads in the tiles before (after the scan: plus the cursor)
+    unsigned long long run_head;    // 1 + the position of the last run head in them, 0: none
+    unsigned long long chain_head;  // ... of the last chain head
+    unsigned long long win_head;    // ... of the last first window of a stretch of windows
+};
+// the control words are kc_path_stats
+enum : int { PC_SEQS = 0, PC_WINDOWS, PC_LOCATED, PC_RUNS, PC_CHAINS, PC_THREADED, PATH_CTL_WORDS = 8 };
+// (one position past the pass takes the first_run of the empty sequences at its end)
+inline uint64_t path_tiles(uint64_t n_pos) { return n_pos / PATH_T + 1; }
+struct PathPass {
+    const uint2* place;
+    uint64_t n_pos, base;
+    const uint64_t* off;
+    uint64_t i0, i1;
+    int k;
+};
+template <int W>
+struct PathOps {
+    static hipError_t locate(TableView t, PackedView sv, UnitigBufs u, int k, uint64_t n_pos, uint64_t n_sym,
+                             uint2* place, hipStream_t s);
+};
+hipError_t launch_path_locate(TableView t, PackedView sv, UnitigBufs u, int k, uint64_t n_pos, uint64_t n_sym,
+                              uint2* place, hipStream_t s);
+hipError_t launch_path_runs(PathPass p, UnitigBufs u, int rounds, const uint32_t* rec, PathTile* tiles, void* runs,
+                            uint64_t cap_runs, kc_path_seq* seq, unsigned long long* ctl, hipStream_t s);
+hipError_t launch_path_finish(const kc_path_seq* seq, uint64_t i0, uint64_t i1, unsigned long long* ctl, hipStream_t s);
+
+// Width dispatch of the launchers (kc_count.hip, kc_util.hip, kc_seq.hip, kc_correct.hip, kc_unitig.hip, kc_path.hip): Ops is WOps, CompactOps, QueryOps, SeqOps,
+// JoinOps, GraphOps, UnitigOps, CleanOps, BubbleOps, WeakOps, CorrectOps or PathOps, whose members are defined and explicitly instantiated by the translation unit of their width
+// (kc_count_w.hip, kc_compact_w.hip, kc_query_w.hip, kc_seq_w.hip, kc_join_w.hip, kc_graph_w.hip, kc_unitig_w.hip, kc_clean_w.hip, kc_bubble_w.hip, kc_weak_w.hip, kc_correct_w.hip, kc_path_w.hip -DKC_W=W, W = 1..MAX_W).  No extern template
 // list is needed beside it: the members have no definition in any other translation unit, so
 // nothing there can instantiate them implicitly.
 #define KC_DISPATCH(Ops, W_, CALL)             \

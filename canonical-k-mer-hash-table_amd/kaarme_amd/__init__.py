@@ -67,6 +67,7 @@ EXPORTS = (
     "kc_neighbors_device", "kc_neighbors", "kc_graph_device", "kc_graph",
     "kc_unitigs_device", "kc_unitigs",
     "kc_unitig_graph_device", "kc_unitig_graph",
+    "kc_read_paths_device", "kc_read_paths",
     "kc_clean_device", "kc_clean",
     "kc_pop_bubbles_device", "kc_pop_bubbles", "kc_cut_weak_device", "kc_cut_weak",
 )
@@ -79,6 +80,14 @@ UNITIG_CIRCULAR = 1  # kc_unitig.flags (KC_UNITIG_CIRCULAR)
 EDGE_FROM_REV, EDGE_TO_REV = 1, 2
 # kc_unitig_edge (include/kc_api.h), 16 bytes
 EDGE_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+# kc_path_run.flags (KC_RUN_*): the run reads its unitig as U-; the window before its first is located too
+RUN_REV, RUN_JOINED = 1, 2
+NO_UNITIG = 0xFFFFFFFF  # KC_NO_UNITIG
+# kc_path_run and kc_path_seq (include/kc_api.h), 32 bytes each
+RUN_DTYPE = np.dtype([("text_pos", "<u8"), ("seq", "<u4"), ("windows", "<u4"), ("unitig", "<u4"), ("pos", "<u4"),
+                      ("flags", "<u4"), ("reserved", "<u4")])
+PATH_SEQ_DTYPE = np.dtype([("first_run", "<u8"), ("windows", "<u4"), ("located", "<u4"), ("runs", "<u4"),
+                           ("chains", "<u4"), ("longest_chain", "<u4"), ("reserved", "<u4")])
 # kc_table_op* operations (KC_OP_*): on the raw counts ca, cb of a key in a and in b
 OP_INTERSECT_MIN, OP_INTERSECT_SUM, OP_INTERSECT_LEFT, OP_SUBTRACT, OP_COUNTS_SUBTRACT, OP_UNION_SUM, OP_UNION_MAX = range(7)
 OP_NAMES = {"intersect-min": OP_INTERSECT_MIN, "intersect-sum": OP_INTERSECT_SUM, "intersect-left": OP_INTERSECT_LEFT,
@@ -106,6 +115,44 @@ def gfa_lines(records, bases, edges, k: int) -> List[str]:
         out.append(f"L\t{a}\t{'-' if fl & EDGE_FROM_REV else '+'}\t{b}\t{'-' if fl & EDGE_TO_REV else '+'}\t{k - 1}M")
     for i in np.flatnonzero(records[:, 3] & np.uint64(UNITIG_CIRCULAR)).tolist():
         out += [f"L\t{i}\t{o}\t{i}\t{o}\t{k - 1}M" for o in "+-"]
+    return out
+
+
+def gaf_lines(names, seqs, records, runs, k: int) -> List[str]:
+    """The read paths as GAF lines (without line ends), what the CLI's --paths-out writes: one line
+    per chain in run order, "name qlen qstart qend + path plen pstart pend matches alnlen 255
+    cg:Z:<alnlen>=".  names and seqs: the sequences of the read_paths call (their text joined by
+    pack_sequences); records, runs: its records and RUN_DTYPE runs.  path is ">i" or "<i" per
+    segment visit, a run that goes round a circle visiting it once per lap; qend - qstart = the
+    chain's windows + k - 1 = matches = alnlen = pend - pstart; plen is the sum of the visited
+    segments' lengths minus k - 1 per junction."""
+    records = np.asarray(records, dtype=np.uint64).reshape(-1, 4)
+    runs = np.asarray(runs, dtype=RUN_DTYPE)
+    starts = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if len(seqs):
+        starts[1:] = np.cumsum([len(s_) + 1 for s_ in seqs])
+    out = []
+    chain = None  # [seq, qstart, path, plen, pstart, windows, visits]
+    def flush():
+        if chain is None:
+            return
+        i, qstart, path, plen, pstart, windows, _ = chain
+        aln = windows + k - 1
+        out.append(f"{names[i]}\t{len(seqs[i])}\t{qstart}\t{qstart + aln}\t+\t{path}\t{plen}\t{pstart}\t{pstart + aln}"
+                   f"\t{aln}\t{aln}\t255\tcg:Z:{aln}=")
+    for r in runs.tolist():
+        text_pos, i, windows, u, q, flags = r[:6]
+        n_nodes, circ = int(records[u, 1]), bool(int(records[u, 3]) & UNITIG_CIRCULAR)
+        if not flags & RUN_JOINED or chain is None:
+            flush()
+            chain = [i, text_pos - int(starts[i]), "", 0, q, 0, 0]
+        laps = (q + windows - 1) // n_nodes + 1 if circ else 1
+        for _ in range(laps):
+            chain[2] += ("<" if flags & RUN_REV else ">") + str(u)
+            chain[3] += n_nodes + k - 1 - (k - 1 if chain[6] else 0)
+            chain[6] += 1
+        chain[5] += windows
+    flush()
     return out
 
 
@@ -198,6 +245,27 @@ class kc_cdbg_stats(ctypes.Structure):  # 64 bytes
     def as_dict(self) -> dict:
         """the seven statistics (without the reserved word)"""
         return {n: int(getattr(self, n)) for n, _ in self._fields_[:7]}
+
+
+class kc_path_run(ctypes.Structure):  # 32 bytes
+    _fields_ = [("text_pos", ctypes.c_uint64), ("seq", ctypes.c_uint32), ("windows", ctypes.c_uint32),
+                ("unitig", ctypes.c_uint32), ("pos", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class kc_path_seq(ctypes.Structure):  # 32 bytes
+    _fields_ = [("first_run", ctypes.c_uint64), ("windows", ctypes.c_uint32), ("located", ctypes.c_uint32),
+                ("runs", ctypes.c_uint32), ("chains", ctypes.c_uint32), ("longest_chain", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class kc_path_stats(ctypes.Structure):  # 64 bytes
+    _fields_ = [("seqs", ctypes.c_uint64), ("windows", ctypes.c_uint64), ("located", ctypes.c_uint64),
+                ("runs", ctypes.c_uint64), ("chains", ctypes.c_uint64), ("threaded", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in ("seqs", "windows", "located", "runs", "chains", "threaded")}
 
 
 class kc_clean_desc(ctypes.Structure):  # 24 bytes
@@ -374,6 +442,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "kc_unitig_graph": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
                                   ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
                                   ctypes.POINTER(ctypes.POINTER(kc_unitig_edge)), ctypes.POINTER(kc_cdbg_stats)]),
+        "kc_read_paths_device": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, P, U64, P, P, U64, P, U64, P, U64,
+                                       P, P, P]),
+        "kc_read_paths": (I32, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(kc_unitig)),
+                                ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
+                                ctypes.POINTER(ctypes.POINTER(kc_unitig_edge)), ctypes.POINTER(kc_cdbg_stats), P, U64, P, U64,
+                                ctypes.POINTER(ctypes.POINTER(kc_path_run)), ctypes.POINTER(ctypes.POINTER(kc_path_seq)),
+                                ctypes.POINTER(kc_path_stats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1040,6 +1115,62 @@ class KmerCounter:
         self._chk(self.lib.kc_unitig_graph(self._ctx, min_count, max_count, None, None, None, ctypes.byref(st)),
                   "kc_unitig_graph")
         return st.as_dict()
+
+    # -- read paths through the compacted graph (kc_read_paths*)
+    def read_paths_device(self, text_ptr: int, n_bytes: int, offsets, min_count: int = 1, max_count: int = 0,
+                          unitigs_ptr: int = 0, cap_unitigs: int = 0, bases_ptr: int = 0, cap_bases: int = 0,
+                          edges_ptr: int = 0, cap_edges: int = 0, cdbg_stats_ptr: int = 0, runs_ptr: int = 0,
+                          cap_runs: int = 0, seq_ptr: int = 0, path_stats_ptr: int = 0, stream: int = 0):
+        """unitig_graph_device plus the paths of a text in device memory through that graph: sequence
+        i is the bytes [offsets[i], offsets[i + 1]) (host offsets); a 32-byte kc_path_run per run at
+        runs_ptr in text order (run j only when j < cap_runs), a kc_path_seq per sequence at seq_ptr
+        and the 64-byte kc_path_stats, always the full totals, at path_stats_ptr; each pointer may be
+        0.  Enqueued on `stream`, no wait."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_seqs = max(len(off) - 1, 0)
+        v = lambda x: ctypes.c_void_p(x or None)
+        self._chk(self.lib.kc_read_paths_device(self._ctx, min_count, max_count, v(unitigs_ptr), cap_unitigs, v(bases_ptr),
+                                                cap_bases, v(edges_ptr), cap_edges, v(cdbg_stats_ptr), v(text_ptr), n_bytes,
+                                                off.ctypes.data if len(off) else None, n_seqs, v(runs_ptr), cap_runs,
+                                                v(seq_ptr), v(path_stats_ptr), v(stream)), "kc_read_paths_device")
+
+    def read_paths(self, seqs: Sequence, min_count: int = 1, max_count: int = 0):
+        """(records, bases, edges, cdbg statistics, runs, per-sequence array, path statistics): the
+        compacted graph as unitig_graph() gives it and, through the same call's records, the paths of
+        the sequences (str or bytes): a RUN_DTYPE array in text order (text_pos counts in
+        pack_sequences' text), a PATH_SEQ_DTYPE array and the totals.  gaf_lines writes them as GAF."""
+        text, off = pack_sequences(seqs)
+        n_seqs = len(off) - 1
+        pr, pb, pe = ctypes.POINTER(kc_unitig)(), ctypes.POINTER(ctypes.c_uint8)(), ctypes.POINTER(kc_unitig_edge)()
+        pu, ps = ctypes.POINTER(kc_path_run)(), ctypes.POINTER(kc_path_seq)()
+        st, pst = kc_cdbg_stats(), kc_path_stats()
+        self._chk(self.lib.kc_read_paths(self._ctx, min_count, max_count, ctypes.byref(pr), ctypes.byref(pb),
+                                         ctypes.byref(pe), ctypes.byref(st), text, len(text), off.ctypes.data, n_seqs,
+                                         ctypes.byref(pu), ctypes.byref(ps), ctypes.byref(pst)), "kc_read_paths")
+        try:
+            recs = (np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint64)), shape=(st.unitigs * 4,)).copy()
+                    if st.unitigs else np.zeros(0, dtype=np.uint64))
+            bases = np.ctypeslib.as_array(pb, shape=(st.bases,)).copy() if st.bases else np.zeros(0, dtype=np.uint8)
+            edges = (np.ctypeslib.as_array(ctypes.cast(pe, ctypes.POINTER(ctypes.c_uint32)), shape=(st.edges * 4,)).copy()
+                     if st.edges else np.zeros(0, dtype=np.uint32))
+            runs = (np.ctypeslib.as_array(ctypes.cast(pu, ctypes.POINTER(ctypes.c_uint32)), shape=(pst.runs * 8,)).copy()
+                    if pst.runs else np.zeros(0, dtype=np.uint32))
+            per = (np.ctypeslib.as_array(ctypes.cast(ps, ctypes.POINTER(ctypes.c_uint32)), shape=(n_seqs * 8,)).copy()
+                   if n_seqs else np.zeros(0, dtype=np.uint32))
+        finally:
+            for p_ in (pr, pb, pe, pu, ps):
+                self.lib.kc_free(p_)
+        return (recs.reshape(-1, 4), bases, edges.view(EDGE_DTYPE), st.as_dict(), runs.view(RUN_DTYPE),
+                per.view(PATH_SEQ_DTYPE), pst.as_dict())
+
+    def read_path_stats(self, seqs: Sequence, min_count: int = 1, max_count: int = 0) -> dict:
+        """The path totals of the sequences without records or runs: seqs, windows, located, runs,
+        chains and threaded (sequences whose windows form one chain)."""
+        text, off = pack_sequences(seqs)
+        pst = kc_path_stats()
+        self._chk(self.lib.kc_read_paths(self._ctx, min_count, max_count, None, None, None, None, text, len(text),
+                                         off.ctypes.data, len(off) - 1, None, None, ctypes.byref(pst)), "kc_read_paths")
+        return pst.as_dict()
 
     # -- graph cleaning (kc_clean*): this counter is the destination
     def clean_device(self, src: "KmerCounter", min_count: int = 1, max_count: int = 0, tip_max_nodes: int = 0,

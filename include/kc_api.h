@@ -707,6 +707,94 @@ int kc_unitig_graph_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, 
 int kc_unitig_graph(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
                     kc_unitig_edge** edges, kc_cdbg_stats* stats);   /* kc_free all three */
 
+/* Read paths: where every sequence of a text lies in the compacted graph -- what SPAdes, MEGAHIT and
+ * Velvet thread reads through the graph for, what Bifrost and pufferfish answer per k-mer (which
+ * unitig, which offset, which strand), what GraphAligner and Bandage read as GAF beside the GFA.
+ * Record indices differ from launch to launch, so a path can only name the unitigs of the call that
+ * wrote them: one call writes graph and paths together.  All terms of kc_graph_device,
+ * kc_unitigs_device, kc_unitig_graph_device and kc_seq_stats_device hold: node, range, unitig, S_U,
+ * orientation (orient(S_U, 0) = S_U, orient(S_U, 1) = rc(S_U)), palindromic unitig, circular, the
+ * text and its break bytes, the offsets array, a sequence's windows (never spanning two sequences).
+ *   located window  a window at text position p whose canonical k-mer is a node of the range.  Its
+ *                 place is (U, rev, q): U the record index of the node's unitig; rev = 0 when the
+ *                 window's k bases, upper-cased, read as the node reads inside S_U, else 1 (always 0
+ *                 on a palindromic unitig); q the index of that k-mer in orient(S_U, rev), so
+ *                 orient(S_U, rev)[q .. q + k) equals the window's bases.
+ *   run           a maximal set of windows at consecutive positions p, p + 1, ... of one sequence,
+ *                 all located on the same U with the same rev, whose q grows by one per window; on
+ *                 a circular unitig q steps from n_nodes - 1 to 0, so a run may go round a circle
+ *                 any number of times and `windows` may exceed n_nodes.  The rule is arithmetic on
+ *                 (U, rev, q), the unitig's n_nodes and its circular flag; nothing is probed twice.
+ *   joined        a run is joined when the window at p - 1 of the same sequence is located too (it
+ *                 belongs to the run before).  A chain is a maximal sequence of runs each joined to
+ *                 the one before: a maximal stretch of consecutive located windows.
+ *   properties    a joined run starts at q = 0, and the run before it ends at the last k-mer of its
+ *                 oriented unitig.  For two such runs (U, a) then (V, b) the tuple (U, a, V, b) is in
+ *                 the same call's edge list (a palindromic unitig's bit reads 0 there), except U == V
+ *                 circular with a == b, which the run rule has merged already.  No run on a circular
+ *                 unitig is joined or followed by a joined run.  Along a chain the text equals the
+ *                 walk's string.
+ *   kc_read_paths_device  the graph part is kc_unitig_graph_device's, unchanged in every rule and run
+ *                 by the same host code.  The text part runs after the call's last records launch,
+ *                 whose numbering the caller receives.  dev_text, n_bytes, offsets (HOST array of
+ *                 n_seqs + 1 entries) and n_seqs are kc_seq_stats_device's.  Runs are written in
+ *                 ascending text_pos order -- hence sequence by sequence; this order is specified,
+ *                 unlike the records' and the edges'.  Run j is written only when j < cap_runs and
+ *                 nothing past it; *dev_path_stats, and first_run and runs of every kc_path_seq, hold
+ *                 the full totals whatever the capacity, so a statistics-only call sizes the next.
+ *                 `unitig` is a valid number of the unbounded record numbering even where
+ *                 cap_unitigs cut the records.  Every output pointer may be NULL; dev_edges and
+ *                 dev_runs are 16-byte aligned, as every device allocation is (else KC_ERR_ARG).  The
+ *                 text runs in passes cut at sequence boundaries of at most kc_config.batch_bytes,
+ *                 a longer single sequence being a pass of its own; the run numbering carries from
+ *                 pass to pass on the device.  No host wait beyond an earlier call's offsets copy.
+ *   kc_read_paths  the same in host memory of the exact sizes (kc_free the five arrays); any
+ *                 out-pointer may be NULL; waits.  The ranking runs once; the text part runs twice,
+ *                 the first time without buffers for the number of runs.
+ * The errors are kc_unitig_graph*'s and kc_seq_stats*'s; KC_ERR_NOMEM comes before any kernel of
+ * the device form.  An emptied table gives zero unitigs and zero runs, every window unlocated;
+ * n_bytes = 0 and n_seqs = 0 are KC_OK.  The table is only read and no counter of kc_stats changes.
+ * Kernels: one fused pass from the packed text to a place per position (one probe and four gathers
+ * per window, no key through HBM), then per tile of 256 positions the run heads, one workgroup's
+ * scan of the tiles, and the emit, where every run's LAST window writes its record (the heads before
+ * it number it, the last head before it starts it); the per-sequence sums are atomics per run, chain
+ * and stretch of windows.  Scratch per pass, on top of kc_unitig_graph*'s:
+ *   scratch = 5 * table_slots + 144 * ids + 8.5 * pass bytes,
+ * 8 bytes of place and 3/8 byte of packed text per text byte and 32 bytes per 256; 32 bytes per
+ * sequence of the text more when dev_seq is NULL. */
+#define KC_RUN_REV    1u   /* kc_path_run.flags: the run reads its unitig as U- */
+#define KC_RUN_JOINED 2u   /* kc_path_run.flags: the window before its first is located too */
+#define KC_NO_UNITIG  0xFFFFFFFFu
+typedef struct {            /* 32 bytes, written with 16-byte stores */
+    uint64_t text_pos;      /* byte offset of the run's first window in the text */
+    uint32_t seq;           /* index of its sequence */
+    uint32_t windows;       /* consecutive window starts text_pos .. text_pos + windows - 1 */
+    uint32_t unitig;        /* record index of this call's kc_unitig records */
+    uint32_t pos;           /* q of the first window in orient(S_U, rev) */
+    uint32_t flags;         /* KC_RUN_REV | KC_RUN_JOINED; every other bit 0 */
+    uint32_t reserved;      /* 0 */
+} kc_path_run;
+typedef struct {            /* 32 bytes */
+    uint64_t first_run;     /* index of the sequence's first run in the unbounded run numbering */
+    uint32_t windows, located, runs, chains;
+    uint32_t longest_chain; /* windows of its longest chain; == windows > 0: the sequence threads the graph whole */
+    uint32_t reserved;      /* 0 */
+} kc_path_seq;              /* a sequence without windows: first_run as defined, every other field 0 */
+typedef struct {            /* 64 bytes */
+    uint64_t seqs, windows, located, runs, chains;
+    uint64_t threaded;      /* sequences with windows > 0 and longest_chain == windows */
+    uint64_t reserved[2];   /* 0 */
+} kc_path_stats;
+int kc_read_paths_device(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig* dev_unitigs,
+                         uint64_t cap_unitigs, uint8_t* dev_bases, uint64_t cap_bases, kc_unitig_edge* dev_edges,
+                         uint64_t cap_edges, kc_cdbg_stats* dev_cdbg_stats, const uint8_t* dev_text, uint64_t n_bytes,
+                         const uint64_t* offsets, uint64_t n_seqs, kc_path_run* dev_runs, uint64_t cap_runs,
+                         kc_path_seq* dev_seq, kc_path_stats* dev_path_stats, void* hip_stream);
+int kc_read_paths(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, kc_unitig** unitigs, uint8_t** bases,
+                  kc_unitig_edge** edges, kc_cdbg_stats* cdbg_stats, const uint8_t* text, uint64_t n_bytes,
+                  const uint64_t* offsets, uint64_t n_seqs, kc_path_run** runs, kc_path_seq** seq,
+                  kc_path_stats* path_stats);   /* kc_free all five */
+
 /* Graph cleaning: the graph of src's range without its short tips and its short isolated unitigs,
  * as a new counted table -- the step Bifrost (-i, -d), Minia, MEGAHIT and Velvet run on the raw
  * graph of sequencing reads before anything else.  All terms are kc_graph_device's and
