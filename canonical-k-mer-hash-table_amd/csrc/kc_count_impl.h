@@ -36,6 +36,7 @@
 #include <cstring>
 
 #include "kc_common.h"
+#include "kc_slot_mask.h"
 #include "kc_table_insert.h"
 #include "kc_table_read.h"
 
@@ -1485,19 +1486,18 @@ DEV uint32_t lds_chunk(uint32_t b, uint32_t q) { return b * 8 + (q ^ ((b >> 1) &
 DEV uint64_t* lds_word(uint64_t* lt, uint32_t b, uint32_t word) {
     return lt + lds_chunk(b, word >> 1) * 2 + (word & 1);
 }
+// The same address from a bucket's two terms, which a probe step computes once: its first byte
+// lb = lt + 128 b and its swizzle swz = 16 ((b >> 1) & 7).  Word `word` of the bucket is at byte
+// (8 word) ^ swz: bit 3 of 8 word is the word's half of its chunk, bits 4.. the chunk.
+DEV uint8_t* lds_bucket(uint64_t* lt, uint32_t b) { return reinterpret_cast<uint8_t*>(lt) + (b << 7); }
+DEV uint32_t lds_swz(uint32_t b) { return (b << 3) & 0x70u; }
+DEV uint64_t* lds_word8(uint8_t* lb, uint32_t swz, uint32_t word8) {
+    return reinterpret_cast<uint64_t*>(lb + (word8 ^ swz));
+}
 
 // 8-bit slot tags (LDS only, beside the region image): one u64 per bucket, byte s = the tag
 // of slot s, 0 = empty.  A probe reads the bucket's tags (one ds_read_b64) and the key words
-// of the slots whose tag matches, instead of every key word of the bucket.
-DEV uint32_t slot_tag(uint64_t t0) { return 1u + (((uint32_t)t0 & 0xFFu) * 255u >> 8); }
-// bit i set iff byte i of x is zero (exact: no borrow between bytes)
-DEV uint32_t zero_byte_mask4(uint32_t x) {
-    const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);  // bit 7 of each zero byte
-    return ((z >> 7) * 0x01020408u) >> 24;                                       // bits 7/15/23/31 -> 0..3
-}
-DEV uint32_t zero_byte_mask8(uint64_t x) {
-    return zero_byte_mask4((uint32_t)x) | zero_byte_mask4((uint32_t)(x >> 32)) << 4;
-}
+// of the slots whose tag matches, instead of every key word of the bucket (kc_slot_mask.h).
 
 // Exclusive prefix of a level-3 workgroup's n <= MAX_SEG_GROUP segment fills (s_pre[0..n],
 // s_pre[n] = total), by the first wave: two fills per lane, one DPP scan (was a one-thread loop
@@ -1623,6 +1623,8 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
     // [cb, nb), both bounds in registers
     uint32_t cs = 0, cb = 0, nb = 0;
     if constexpr (SEG) nb = s_pre[1];
+    // ... and its first item's index in the key array, formed again only when the cursor moves
+    uint64_t sfirst = SEG ? r * pb.B2 * pb.cap2 : 0;
     // Runs (the merge over region-sorted groups): a sender's records sit in its table order,
     // i.e. sorted by home bucket, and inserted in that order neighbouring lanes collide on
     // the same buckets and banks.  The items are visited in a scrambled order instead: a
@@ -1642,6 +1644,16 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
     // pass's fine bins: against the fine bin's)
     const bool r12_reg = r12 && (pb.rec12 & R12_REG);
     const uint32_t xlo_r = REC6 || r12_reg ? (uint32_t)region_xlo(r, tv.R) : 0;
+    // The start bucket of a 6-byte record, decoded against the region's lowest x: x = xlo_r + d, so
+    // the fraction x R mod 2^32 is (xlo_r R mod 2^32) + d R: a wave-uniform term and, with d < 2^16 and
+    // R < 2^24 (6-byte records are written only for such R, launch_part_w), one 24-bit multiply-add
+    // without forming x.  (The uniform term through readfirstlane: left visible, the two terms are
+    // folded back into a 32-bit multiply of x.  12-byte records against the region keep
+    // bucket_in_region: a subtraction and the 24-bit form are no fewer instructions than the 32-bit
+    // multiply, which issues at less than twice an add's cost, tools/probe/p_mulcost.hip.)
+    const uint32_t R24 = (uint32_t)tv.R & 0xFFFFFFu;
+    const uint32_t xlo_frac = __builtin_amdgcn_readfirstlane(xlo_r * (uint32_t)tv.R);
+    auto bucket_from_xlo = [&](uint32_t d) -> uint32_t { return (xlo_frac + __umul24(d, R24)) >> (32 - BPR_BITS); };
     // sg: Rec12 items' fine bin (seg >> r12_b2s), beside the raw record
     auto load_items = [&](uint64_t base, uint64_t (&kk)[KB][W], uint64_t (&add)[KB], uint32_t& ok,
                           uint32_t (&sg)[KB]) {
@@ -1654,19 +1666,23 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
                 // used, or two whole words) by one 16-byte load into the same registers, at the
                 // format's byte offset (k_p2f load_tile: format-specific registers made every load
                 // wait for the earlier ones); lanes past the end load their segment's first item
-                uint64_t seg = r * pb.B2 + cs, item = seg * pb.cap2;
+                uint64_t item = sfirst;
                 if (i < end) {
-                    while (nb <= i) {
-                        cs++;
-                        cb = nb;
-                        nb = s_pre[cs + 1];
+                    if (nb <= i) {
+                        do {
+                            cs++;
+                            cb = nb;
+                            nb = s_pre[cs + 1];
+                        } while (nb <= i);
+                        sfirst = (r * pb.B2 + cs) * pb.cap2;
                     }
-                    seg = r * pb.B2 + cs;
-                    item = seg * pb.cap2 + (i - cb);
+                    item = sfirst + (i - cb);
                     ok |= 1u << q;
                 }
+                const uint64_t seg = r * pb.B2 + cs;
                 uint32_t v[4];
-                __builtin_memcpy(v, reinterpret_cast<const uint8_t*>(pb.keys2) + (r12 ? item * 12 : item * 16), 16);
+                // (12 or 16 bytes per item by shift-adds)
+                __builtin_memcpy(v, reinterpret_cast<const uint8_t*>(pb.keys2) + ((item << 3) + (item << (r12 ? 2 : 3))), 16);
                 kk[q][0] = v[0] | (uint64_t)v[1] << 32;
                 kk[q][1] = v[2] | (uint64_t)v[3] << 32;
                 sg[q] = (uint32_t)(seg >> pb.r12_b2s);
@@ -1692,18 +1708,21 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
                 }
             } else if (i < end) {
                 if constexpr (SEG) {
-                    while (nb <= i) {
-                        cs++;
-                        cb = nb;
-                        nb = s_pre[cs + 1];
+                    if (nb <= i) {
+                        do {
+                            cs++;
+                            cb = nb;
+                            nb = s_pre[cs + 1];
+                        } while (nb <= i);
+                        sfirst = (r * pb.B2 + cs) * pb.cap2;
                     }
-                    src = pb.keys2 + ((r * pb.B2 + cs) * pb.cap2 + (i - cb)) * IW;
+                    src = pb.keys2 + (sfirst + (i - cb)) * IW;
                 } else {
                     src = pb.keys2 + i * IW;
                 }
             }
             ok |= (src != nullptr) << q;
-            if (!src) src = pb.keys2 + (SEG ? (r * pb.B2 + cs) * pb.cap2 * IW : start * IW);  // (a nearby item)
+            if (!src) src = pb.keys2 + (SEG ? sfirst * IW : start * IW);  // (a nearby item)
 #pragma unroll
             for (int w = 0; w < W; w++) kk[q][w] = ks_load(src + w);
             if constexpr (CNT) add[q] = src[W];  // (raw: CNT_MASK applied where it is used)
@@ -1711,34 +1730,41 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
         }
     };
 
-    // one key into the LDS region (tag probe, claim by CAS on word 0, count add); false: the
-    // region's probe bound was reached (counted as an overflow)
-    auto insert_one = [&](const uint64_t (&kw)[W], uint64_t a0) -> bool {
+    // one key into the LDS region (tag probe, claim by CAS on word 0, count add), from its start
+    // bucket b; false: the region's probe bound was reached (counted as an overflow)
+    // The candidate masks stay in byte-lane form (kc_slot_mask.h), so a slot is known as s8 = 8 *
+    // slot: key word w of it is word8 s8 W + 8 w of the bucket, its count word8 8 S W + s8 (one-word
+    // keys: the key word's address with byte bit 6 flipped).
+    typedef SlotMask<S> SM;
+    auto insert_one = [&](const uint64_t (&kw)[W], uint64_t a0, uint32_t b) -> bool {
         const uint64_t k0 = kw[0];
-        uint32_t b = bucket_in_region(k0, tv.R);
         bool done = false;
         {
-            constexpr uint32_t SMASK = (1u << S) - 1;
+            constexpr uint32_t NONE = ~0u;
             const uint32_t tag = slot_tag(k0);
-            const uint64_t bc = 0x0101010101010101ULL * tag;
+            const uint32_t t4 = slot_tag4(tag);
             for (int probe = 0; probe < 4 * BPR && !done;) {
-                const uint64_t tw = tg[b];
-                uint32_t m = zero_byte_mask8(tw ^ bc) & SMASK;
-                int slot = -1;
+                uint8_t* const lb = lds_bucket(lt, b);
+                const uint32_t swz = lds_swz(b);
+                uint64_t tw;
+                if constexpr (SM::HALF) tw = *reinterpret_cast<const uint32_t*>(tg + b);  // (slots 4.. do not exist)
+                else tw = tg[b];
+                typename SM::mask_t m = SM::match(tw, t4);
+                uint32_t s8 = NONE;
                 while (m) {  // candidates: usually none (new key) or exactly the key's slot
-                    const int sl = __builtin_ctz(m);
-                    m &= m - 1;
-                    bool eq = *lds_word(lt, b, sl * W) == k0;
+                    const uint32_t c8 = SM::first8(m);
+                    m = SM::rest(m);
+                    bool eq = *lds_word8(lb, swz, c8 * W) == k0;
 #pragma unroll
-                    for (int w = 1; w < W; w++) eq &= *lds_word(lt, b, sl * W + w) == kw[w];
+                    for (int w = 1; w < W; w++) eq &= *lds_word8(lb, swz, c8 * W + 8 * w) == kw[w];
                     if (eq) {
-                        slot = sl;
+                        s8 = c8;
                         break;
                     }
                 }
                 uint64_t a = a0;
-                if (slot < 0) {
-                    const uint32_t em = zero_byte_mask8(tw) & SMASK;
+                if (s8 == NONE) {
+                    const typename SM::mask_t em = SM::empty(tw);
                     if (!em) {  // bucket full, key absent: next bucket
                         b = (b + 1) & (BPR - 1);
                         probe++;
@@ -1746,28 +1772,30 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
                     }
                     // claim the first untagged slot by its word 0; the tag is stored last, so
                     // a tag match always finds the key's words published
-                    const int e = __builtin_ctz(em);
-                    const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long*>(lds_word(lt, b, e * W)),
+                    const uint32_t e8 = SM::first8(em);
+                    const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long*>(lds_word8(lb, swz, e8 * W)),
                                                    0ULL, (unsigned long long)k0);
                     if (old == EMPTY) {
 #pragma unroll
                         for (int w = 1; w < W; w++)
-                            __hip_atomic_store(lds_word(lt, b, e * W + w), kw[w], __ATOMIC_RELAXED,
+                            __hip_atomic_store(lds_word8(lb, swz, e8 * W + 8 * w), kw[w], __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_WORKGROUP);
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        __hip_atomic_store(reinterpret_cast<uint8_t*>(tg + b) + e, (uint8_t)tag, __ATOMIC_RELAXED,
+                        __hip_atomic_store(reinterpret_cast<uint8_t*>(tg + b) + (e8 >> 3), (uint8_t)tag, __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_WORKGROUP);
                         if constexpr (W > 1) a += READY;  // the table format's published flag
-                        slot = e;
+                        s8 = e8;
                     } else if (W == 1 && old == k0) {
-                        slot = e;  // the same key, claimed an instant ago
+                        s8 = e8;  // the same key, claimed an instant ago
                     } else {
                         probe++;  // claimed by another key (tag not yet stored): read again
                         continue;
                     }
                 }
-                atomicAdd(reinterpret_cast<unsigned long long*>(lds_word(lt, b, S * W + slot)),
-                          (unsigned long long)a);
+                uint64_t* cw;
+                if constexpr (W == 1) cw = reinterpret_cast<uint64_t*>(lb + ((s8 ^ swz) ^ 0x40u));
+                else cw = lds_word8(lb, swz, 8 * S * W + s8);
+                atomicAdd(reinterpret_cast<unsigned long long*>(cw), (unsigned long long)a);
                 done = true;
             }
         }
@@ -1784,6 +1812,12 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
         constexpr int KP = GATE ? 2 : 4;  // (the gate's filter words: 4 pairs spill)
         const uint32_t endp = __builtin_amdgcn_readfirstlane(s_pp[pb.B2]);  // (uniform: scalar branches)
         uint32_t ps = 0, pcb = 0, pnb = s_pp[1], pfill = s_pre[1];
+        // psb: pair j of the cursor's segment is at byte psb + 12 j of the key array -- the segment's
+        // first pair less pcb, times 12 (modulo 2^64), formed again only when the cursor moves.
+        // 12 j = (j << 3) + (j << 2) by 64-bit shift-adds
+        const uint8_t* const k2b = reinterpret_cast<const uint8_t*>(pb.keys2);
+        auto seg_bytes = [&]() -> uint64_t { return (((r * pb.B2 + ps) * pb.cap2 >> 1) - pcb) * 12; };
+        uint64_t psb = seg_bytes();
         auto load_pairs = [&](uint32_t base, uint3 (&v)[KP], uint32_t& ok) {
             // the pairs' addresses first (the segment cursor's loop), then every load back to back
             uint64_t pp[KP];
@@ -1793,13 +1827,16 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
                 const uint32_t j = base + threadIdx.x + (uint32_t)q * NT;
                 pp[q] = 0;
                 if (j < endp) {  // (loads only in range, as the one-record form)
-                    while (pnb <= j) {
-                        ps++;
-                        pcb = pnb;
-                        pnb = s_pp[ps + 1];
+                    if (pnb <= j) {
+                        do {
+                            ps++;
+                            pcb = pnb;
+                            pnb = s_pp[ps + 1];
+                        } while (pnb <= j);
                         pfill = s_pre[ps + 1] - s_pre[ps];
+                        psb = seg_bytes();
                     }
-                    pp[q] = ((r * pb.B2 + ps) * pb.cap2 >> 1) + (j - pcb);
+                    pp[q] = psb + ((uint64_t)j << 3) + ((uint64_t)j << 2);
                     ok |= (1u | (uint32_t)(2 * (j - pcb) + 1 < pfill) << 1) << (2 * q);
                 }
             }
@@ -1808,7 +1845,7 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
 #pragma unroll
             for (int q = 0; q < KP; q++) {
                 uint32_t w3[3];
-                __builtin_memcpy(w3, reinterpret_cast<const uint32_t*>(pb.keys2) + pp[q] * 3, 12);
+                __builtin_memcpy(w3, reinterpret_cast<const uint32_t*>(k2b + pp[q]), 12);
                 v[q] = make_uint3(w3[0], w3[1], w3[2]);
             }
         };
@@ -1842,7 +1879,8 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
             }
 #pragma unroll
             for (int q = 0; q < 2 * KP; q++)
-                if (pass[q] && !insert_one(kp[q], 1)) n_fail++;
+                if (pass[q] && !insert_one(kp[q], 1, bucket_from_xlo(q & 1 ? cv[q / 2].z >> 16 : cv[q / 2].z & 0xFFFFu)))
+                    n_fail++;
 #pragma unroll
             for (int q = 0; q < KP; q++) cv[q] = nv[q];
             cok = nok;
@@ -1884,7 +1922,7 @@ __global__ __launch_bounds__(P3_THREADS, P3_THREADS / 128) void k_p3(TableView t
             }
 #pragma unroll
             for (int q = 0; q < KB; q++)
-                if (pass[q] && !insert_one(it.kk[q], it.add[q])) n_fail++;
+                if (pass[q] && !insert_one(it.kk[q], it.add[q], bucket_in_region(it.kk[q][0], tv.R))) n_fail++;
         };
         constexpr uint64_t STEP = (uint64_t)KB * NT;
         if constexpr (W <= 2) {
@@ -2690,7 +2728,8 @@ static hipError_t launch_part_w(PackedView sym, int k, TableView t, BloomView bf
     hipError_t e;
     const unsigned long long* gate = &ctr->part_overflow;
     // one-word keys in a table of >= 2^16 regions: 6-byte level-2 records (StoreRec6)
-    pb.rec6 = W == 1 && t.R >= (1ULL << 16);
+    // (and fewer than 2^24, a table of 1 TiB: k_p3 takes a record's start bucket by a 24-bit multiply)
+    pb.rec6 = W == 1 && t.R >= (1ULL << 16) && t.R < (1ULL << 24);
     // two-word keys: 12-byte records at each level whose bins span few enough values of x
     if constexpr (W == 2) set_rec12_table(pb, t, k);
     if (phase & PH_L3) {  // the deferred level 3 of a group of batches: B2 = the group's segments

@@ -158,10 +158,10 @@ inline int span_bits32(uint64_t span) {
     return b;
 }
 // the level-2 record of the counting pass in a table of R regions (kc_count_impl.h
-// launch_part_w): 6 bytes for one-word keys once R >= 2^16 (StoreRec6), 12 for two-word keys
+// launch_part_w): 6 bytes for one-word keys once 2^16 <= R < 2^24 (StoreRec6), 12 for two-word keys
 // whose region spans few enough values of x (Rec12: hb + 1 + xb2 <= 32), else the W key words
 inline uint64_t level2_record_bytes(int W, int k, uint64_t R) {
-    if (W == 1) return R >= (1ULL << 16) ? 6 : 8;
+    if (W == 1) return R >= (1ULL << 16) && R < (1ULL << 24) ? 6 : 8;
     if (W == 2 && R) {
         const int hb = 2 * k - 96 > 0 ? 2 * k - 96 : 0;
         if (hb + 1 + span_bits32(((1ULL << 32) + R - 1) / R) <= 32) return 12;
